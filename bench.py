@@ -8,8 +8,14 @@ scaling). Default exchange (--dp-mode sharded, harness/sharded.py): every rank O
 and ships 56-byte projected records to the renderers, which return 36-byte pixel-space gradient accumulators; K12 + Adam run
 on the owner's shard. --dp-mode zero1|allreduce: replicated parameters, the 236-B/Gaussian gradient crosses xGMI instead.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S1|S2|S3] [--no-cpu-baseline] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scene S1|S2|S3] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-extras] [--no-pmc] [--blocks B] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last two timed iterations replayed on the seeded model
+(--dump-outputs) and prints the headline. Everything else the line can carry -- realised V / I / B, the stage profile and roofline,
+repeatability blocks, peak memory, live counters, the other exchange, the render / fused / layered / trained-like / surface extras, the CPU
+baseline -- is measured with --full only.
 
 Prints ONE JSON line on rank 0.
 """
@@ -41,6 +47,15 @@ def parse():
     ap.add_argument('--ply', default='', help='bench a trained scene instead of the synthetic one: a 3DGS / FasterGS PLY export (Model.py:511-542 layout), '
                                               'viewed from 8 orbit cameras around its centroid (the training cameras are not in a PLY; +y is taken as down)')
     ap.add_argument('--opacity-shift', type=float, default=0.0, help='added to every opacity logit of the scene (-3 = the "layered" regime of the extras; used by its counter passes)')
+    ap.add_argument('--full', action='store_true', help='measure everything beside the headline as well (realised V / I / B, stage profile, roofline, '
+                                                       'repeatability, peak memory, counters, other exchange, extras, CPU baseline); a plain run '
+                                                       'times the headline only, and the options below that shape these measurements apply with --full')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, run the last two timed iterations (their views; on one GPU also their learning-rate steps) once '
+                         'more on the seeded initial model and write what the second returns to DIR/<name>.npy (float32): the loss (one GPU) or the '
+                         'rendered image (N > 1), and the updated parameters, Adam moments (one GPU) and densification statistics of a fixed seeded '
+                         'sample of 65 536 Gaussians (all of them if fewer). Rank 0 writes; with --dp-mode sharded these are rows of its own shard. '
+                         'The same from run to run, to rounding (see write_dump)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the inference / fused side measurements')
     ap.add_argument('--cpu-baseline-only', action='store_true', help='time only the oracle (no GPU needed)')
@@ -62,7 +77,11 @@ def parse():
     ap.add_argument('--dp-mode', default='sharded', choices=['sharded', 'zero1', 'allreduce'],
                     help="N > 1: 'sharded' = every rank owns N/G Gaussians, 56-B records / 36-B accumulators cross xGMI (harness/sharded.py); "
                          "'zero1' / 'allreduce' = replicated parameters, 236-B gradients cross xGMI (harness/distributed.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    args.full = args.full or args.pmc_child      # the counter passes' child runs the sequence --full measures
+    return args
 
 
 def build_scene(args):
@@ -111,7 +130,7 @@ def live_pmc(args, extra=()) -> dict:
     out: dict = {}
     tmp = tempfile.mkdtemp(prefix='fgs_pmc_', dir='/tmp')
     child = [sys.executable, str(Path(__file__).resolve()), '--scene', args.scene, '--steps', '3', '--warmup', '1', '--no-extras', '--blocks', '1',
-             '--no-cpu-baseline', '--no-pmc', '--pmc-child'] + (['--n-gaussians', str(args.n_gaussians)] if args.n_gaussians else []) \
+             '--no-cpu-baseline', '--no-pmc', '--pmc-child', '--full'] + (['--n-gaussians', str(args.n_gaussians)] if args.n_gaussians else []) \
         + (['--ply', args.ply] if args.ply else []) + list(extra)
     try:
         for tag, counters in (('fetch', ['FETCH_SIZE', 'SQ_INSTS_VALU']), ('write', ['WRITE_SIZE', 'SQ_WAVES'])):
@@ -175,6 +194,29 @@ def cpu_baseline(params, views, stats: dict, budget_s: float = 12.0) -> dict:
                       f'Adam {t_a / done:.2f}s) of the same workload, last view V={last["V"]} I={last["I"]} B32={last["B"]}; '
                       f'OpenMP threads = cores; {total:.1f} s of CPU work',
             'render_mpix_per_s': view.width * view.height / 1e6 / (t_f / done)}
+
+
+DUMP_ROWS = 65_536      # Gaussians sampled by --dump-outputs: 59 floats x 3 (parameter and both moments) x 4 B x 65 536 = 46 MB at SH degree 3
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, last: torch.Tensor, params: dict, moments: dict, densification_info: torch.Tensor) -> None:
+    """--dump-outputs: what the last timed step left its caller, as float32 DIR/<name>.npy. `last` is what the step returned (the loss of the
+    single-GPU iteration, the rendered image of the multi-GPU steps); `params` / `moments` ({'<name>.exp_avg': ...}) / `densification_info`
+    are sampled at the same rows -- a fixed seeded choice of DUMP_ROWS Gaussians -- so that runs with the same arguments compare row for row."""
+    n = densification_info.shape[1]
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values if n > DUMP_ROWS else torch.arange(n)
+    rows = rows.to(densification_info.device)
+    arrays = {('loss' if last.numel() == 1 else 'image'): last.detach().float().cpu().numpy()}
+    for k, t in list(params.items()) + list(moments.items()):
+        arrays[k] = t.detach()[rows].float().cpu().numpy()
+    arrays['densification_info'] = densification_info.detach()[:, rows].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget'
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(d / f'{k}.npy', np.ascontiguousarray(a, dtype=np.float32))
 
 
 def preflight(args, world: int, local_rank) -> None:
@@ -315,6 +357,8 @@ def main():
         for v in {id(v): v for v in my_views}.values():
             S = T.extract_settings(v, g.active_sh_bases, v.background_color)
             targets[id(v)] = be.inference(*pert, S, True, True)
+            if not args.full:
+                continue
             res = be.forward(*g.tensors(), S)
             lay = be.blob_layout(1, n, v.width, v.height, res.state[1], res.state[2])
             n_tiles = ((v.width + 15) // 16) * ((v.height + 11) // 12)
@@ -345,16 +389,15 @@ def main():
 
     vp = make_trainer(args.dp_mode) if use_dp else None
     if vp is not None and hasattr(vp, 'time_comm'):
-        vp.time_comm = world > 1
+        vp.time_comm = world > 1 and args.full      # events around the exchanges: `exposed_comm_ms_per_step` of --full
     settings_of = {id(v): T.extract_settings(v, g.active_sh_bases, v.background_color) for v in views}
 
-    def dp_step(trainer, mode: str, i: int) -> None:
+    def dp_step(trainer, mode: str, i: int) -> torch.Tensor:
         v = my_views[i % len(my_views)]
         if mode == 'sharded':       # every rank names the same global batch: view (i*G + r) is rendered by rank r
             batch = [views[((i % len(my_views)) * world + r) % len(views)] for r in range(world)]
-            trainer.step([settings_of[id(b)] for b in batch], targets[id(v)])
-        else:
-            trainer.step(settings_of[id(v)], targets[id(v)])
+            return trainer.step([settings_of[id(b)] for b in batch], targets[id(v)])
+        return trainer.step(settings_of[id(v)], targets[id(v)])
 
     def step(i: int) -> None:
         if vp is None:
@@ -417,45 +460,110 @@ def main():
             args.dp_mode = 'allreduce'
             vp = make_trainer('allreduce')
             if hasattr(vp, 'time_comm'):
-                vp.time_comm = True
+                vp.time_comm = args.full
     for i in range(len(my_views) if vp is None else 2):
         step(i)
     fence()
-    if not sim:
+    if not sim and args.full:
         torch.cuda.reset_peak_memory_stats(device)
-    # Stage table: a separate, untimed pass of PROFILE_STEPS iterations with HIP events around every stage. The events themselves cost
+    # Stage table (--full): a separate, untimed pass of PROFILE_STEPS iterations with HIP events around every stage. The events themselves cost
     # GPU idle time (~5 us each, ~0.2 ms per iteration with all ~15 stages bracketed: measured with rocprofv3 --kernel-trace), so the
     # timed region below brackets only the dominant stage found here -- the `roofline` figure is still measured live, over the timed steps.
+    # A plain run skips the pass; its timed steps keep their place in the cycle of views all the same, so both time the same views.
     PROFILE_STEPS = 1 if sim else 4
-    be.profile_enable(True)
-    be.profile_read()
-    for i in range(PROFILE_STEPS):
-        step(args.warmup + i)
-    fence()
-    prof = be.profile_read()
-    be.profile_enable(False)
-    n_prof = PROFILE_STEPS
-    dom_stage = max((k for k, v_ in prof.items() if v_[1] > 0 and k in STAGE_KEYS), key=lambda k: prof[k][0] / prof[k][1])
+    if args.full:
+        be.profile_enable(True)
+        be.profile_read()
+        for i in range(PROFILE_STEPS):
+            step(args.warmup + i)
+        fence()
+        prof = be.profile_read()
+        be.profile_enable(False)
+        n_prof = PROFILE_STEPS
+        dom_stage = max((k for k, v_ in prof.items() if v_[1] > 0 and k in STAGE_KEYS), key=lambda k: prof[k][0] / prof[k][1])
     # The W untimed warm-up steps come LAST, directly in front of the timed region (round 6): everything above ends in host-side work (reading the
     # stage profile back) during which the GPU idles for milliseconds, and on some boxes of the pool the first 10-20 iterations after such a pause
     # run 5-15 % slow (tools/diag_spikes.py: the first 10-iteration window after a pause 2.41-2.49 ms against 2.13-2.14 in steady state, the
     # round-5 tree alike: clocks, not code) -- the warm-up is there to absorb exactly that.
     for i in range(args.warmup):
         step(i)
-    be.profile_enable(True, only=dom_stage)
-    be.profile_read()
+    if args.full:
+        be.profile_enable(True, only=dom_stage)
+        be.profile_read()
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(args.warmup + PROFILE_STEPS + i)
     fence()
     elapsed = time.perf_counter() - t0
-    prof_dom = be.profile_read()
-    be.profile_enable(False)
+    if args.full:
+        prof_dom = be.profile_read()
+        be.profile_enable(False)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+
+    def write_dump() -> None:
+        """--dump-outputs, after everything timed: the last TWO timed iterations (their views and targets; on one GPU also their learning-rate
+        steps) applied to the seeded initial model, and what the second hands its caller. Two, so that the dumped step is an Adam step on moments
+        that already hold a gradient -- including the blocks of Gaussians the first view saw and the second does not, whose update only the
+        moments drive. Not the state the timed loop leaves: K11 sums every Gaussian's gradient over its tiles with float atomics, so each
+        iteration agrees with another run only to rounding, and every further iteration starts from that rounding and amplifies it (1.7e-4 of
+        scale after the 33 iterations of a default run against 4e-7 after one) -- the dump must be the same from run to run."""
+        i_last = args.warmup + PROFILE_STEPS + args.steps - 1
+        if vp is None:
+            g_d = T.Gaussians(params, device)
+            g_d.training_setup(training_cameras_extent=5.0)
+            for i in (i_last - 1, i_last):
+                v = my_views[i % len(my_views)]
+                out_last = T.training_iteration(g_d, v, targets[id(v)], i)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, out_last, {k: getattr(g_d, k) for k in T.PARAM_ORDER},
+                             {f'{k}.{m}': g_d.optimizer.state[getattr(g_d, k)][m] for k in T.PARAM_ORDER for m in ('exp_avg', 'exp_avg_sq')},
+                             g_d.densification_info)
+        else:                  # every rank takes part in the steps' exchanges; rank 0 writes its own parameters (sharded: its shard, rows r::G)
+            vp_d = make_trainer(args.dp_mode)
+            for i in (i_last - 1, i_last):
+                out_last = dp_step(vp_d, args.dp_mode, i)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, out_last, dict(vp_d.params), {}, vp_d.densification_info)
+    head = {
+        'metric': 'train_iters_per_sec', 'value': args.steps * world / elapsed, 'unit': 'iters/s (1 view each, whole job)',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
+        'data': ('synthetic; ALL RANKS SHARE cuda:0 (gloo exchanges through host memory): a test of the multi-rank branch on the real kernels, NOT a measurement' if shared else 'synthetic') if not sim
+                else 'synthetic; SIMULATION on CPU (tests/sim build of the HIP sources, gloo): a test of this script, NOT a measurement'}
+    base_config = {'workload': workload + '; full training iteration fwd+loss+bwd+Adam (BASELINE.json configs[2]), loss 0.8*L1+0.2*DSSIM, '
+                                          'densification_info updated', 'parallelism': f'view-parallel dp{world} ({args.dp_mode})' if vp is not None else 'single GPU',
+                   'n_gaussians': n, 'active_sh_bases': g.active_sh_bases,
+                   'forward': 'one host read per pass (fgs_forward)' if not args.async_forward else 'no host synchronisation (fgs_forward_async, capacity = 1.25 x largest instances/Gaussian seen)',
+                   'world': dist.get_world_size() if dist.is_initialized() else 1,
+                   'backend': dist.get_backend() if dist.is_initialized() else 'none (single process)',
+                   'device': 'cpu (simulation)' if sim else f'cuda:{device.index} ({torch.cuda.get_device_name(device)})', 'dp_mode': args.dp_mode if vp is not None else None}
+
+    def own_devices() -> list:
+        """Every rank's device; stops the run if two ranks share one (one process per GPU is required)."""
+        ident = 'cpu' if sim else f'{os.uname().nodename}:{torch.cuda.get_device_properties(device).uuid if hasattr(torch.cuda.get_device_properties(device), "uuid") else device.index}'
+        idents = [None] * world
+        dist.all_gather_object(idents, ident)
+        if not (sim or shared) and len(set(idents)) != world:
+            raise SystemExit(f'bench.py --gpus {world}: ranks share devices ({idents}); one process per GPU is required')
+        return idents
+
+    if not args.full:
+        if world > 1:
+            own_devices()
+        if dp_fallback is not None:
+            head['dp_fallback'] = dp_fallback
+        if args.dump_outputs:
+            write_dump()
+        if rank == 0:
+            emit(json.dumps({**head, 'config': {**base_config, 'measured': 'headline only (plain run); --full adds the realised sizes, stage profile, '
+                                                                              'roofline, repeatability, memory, counters, extras and CPU baseline'}}))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     # Repeatability: the contract's timed region above is ONE block of --steps iterations (49 ms at 20 steps); --blocks - 1 further blocks,
     # each bracketed the same way (barrier + synchronize, maximum over the ranks), say how far one such sample can be trusted.
     block_ms = [elapsed / args.steps * 1e3]
@@ -508,11 +616,7 @@ def main():
     # first SCALE record confirms or kills that per-link model in one run. Every rank must also sit on a device of its own.
     dry = None
     if dist.is_initialized() and world > 1:
-        ident = 'cpu' if sim else f'{os.uname().nodename}:{torch.cuda.get_device_properties(device).uuid if hasattr(torch.cuda.get_device_properties(device), "uuid") else device.index}'
-        idents = [None] * world
-        dist.all_gather_object(idents, ident)
-        if not (sim or shared) and len(set(idents)) != world:
-            raise SystemExit(f'bench.py --gpus {world}: ranks share devices ({idents}); one process per GPU is required')
+        idents = own_devices()
         try:      # (a measurement on the side: it must never take the scaling run down with it)
             link_gbs = 76.8
 
@@ -645,23 +749,15 @@ def main():
                               'avg_kernel_ms_source': f'untimed {n_prof}-step stage-profile pass (HIP events around every stage), not the timed region',
                               'cycles_per_inst': 2.9, 'frac': insts * 2.9 / (1024 * 2.4e9 * max(per_launch[st], 1e-9) * 1e-3)})
     out = {
-        'metric': 'train_iters_per_sec', 'value': args.steps * world / elapsed, 'unit': 'iters/s (1 view each, whole job)',
-        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
-        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-        'data': ('synthetic; ALL RANKS SHARE cuda:0 (gloo exchanges through host memory): a test of the multi-rank branch on the real kernels, NOT a measurement' if shared else 'synthetic') if not sim
-                else 'synthetic; SIMULATION on CPU (tests/sim build of the HIP sources, gloo): a test of this script, NOT a measurement',
-        'config': {'workload': workload + '; full training iteration fwd+loss+bwd+Adam (BASELINE.json configs[2]), loss 0.8*L1+0.2*DSSIM, '
-                               'densification_info updated', 'parallelism': f'view-parallel dp{world} ({args.dp_mode})' if vp is not None else 'single GPU',
-                   'n_gaussians': n, 'visible': V, 'instances': I, 'buckets64': B, 'instances_walked': Ip, 'buckets64_walked': Bp, 'active_sh_bases': K_,
-                   'forward': 'one host read per pass (fgs_forward)' if not args.async_forward else 'no host synchronisation (fgs_forward_async, capacity = 1.25 x largest instances/Gaussian seen)',
+        **head,
+        'config': {**base_config,
+                   'visible': V, 'instances': I, 'buckets64': B, 'instances_walked': Ip, 'buckets64_walked': Bp,
                    'async_forward_overflows': FGS.async_forward_stats()['overflows'],
                    # dense gradients; FusedAdam.step does not read back the zeros of 64-Gaussian blocks without a visible Gaussian when it can prove
                    # the gradient tensors untouched (bit-identical): how often that held / did not in this process
                    'live_block_handover': FGS.live_block_stats(),
-                   'world': dist.get_world_size() if dist.is_initialized() else 1, 'ranks': roster,
+                   'ranks': roster,
                    'rccl_version': '.'.join(str(x) for x in torch.cuda.nccl.version()) if (dist.is_initialized() and not sim and not shared) else None,
-                   'backend': dist.get_backend() if dist.is_initialized() else 'none (single process)',
-                   'device': 'cpu (simulation)' if sim else f'cuda:{device.index} ({torch.cuda.get_device_name(device)})', 'dp_mode': args.dp_mode if vp is not None else None,
                    'wire_bytes_per_rank_per_step': wire_bytes(args.dp_mode) if vp is not None else 0,
                    # sharded exchange on rank 0: time inside the step's three exchanges (counts all-gather, records all-to-all, accumulators
                    # all-to-all), averaged over all blocks incl. warm-up; nothing overlaps them (harness/sharded.py), so exposed = total
@@ -967,6 +1063,8 @@ def main():
             out['cpu_baseline'] = cpu_baseline(params, [v.to('cpu') for v in views], stats)
         except Exception as exc:   # the baseline must never take the GPU number down with it
             out['cpu_baseline'] = {'value': None, 'unit': 'iters/s', 'cores': os.cpu_count(), 'kind': 'port', 'sample': f'failed: {exc}'}
+    if args.dump_outputs:
+        write_dump()
     if rank == 0:
         emit(json.dumps(out))
     if dist.is_initialized():

@@ -1,6 +1,6 @@
 """Generates tests/golden/ref_glue_<scene>.npz and ref_glue_<scene>.trace.json by EXECUTING THE REFERENCE'S OWN PYTHON GLUE.
 
-Build container only (needs /root/reference). The four files torch_bindings/{rasterization,adam,densification,filter3d}.py are loaded from
+Needs a checkout of the reference, named by FGS_REFERENCE_TREE. The four files torch_bindings/{rasterization,adam,densification,filter3d}.py are loaded from
 their path with importlib, unchanged -- never copied into this repository, never shipped -- and run on top of this repository's
 `FasterGSCudaBackend._C` bound to the CPU simulation of the product sources (tests/sim, product flavour). The scenario (tests/ref_glue.py)
 is this repository's own code and only uses the public operator names; what lands in the fixtures is data:
@@ -16,7 +16,9 @@ package's own operators must reproduce the fixture bit for bit on the same simul
 (tests/test_gpu_ref_glue.py). What it does NOT pin: the kernels' arithmetic -- both sides of the comparison run this repository's kernels
 (the reference's are CUDA-only); that remains "parity unpinned" (oracle/fgs_oracle.c header).
 
-Run from the repo root:  python tests/golden/make_ref_glue_golden.py
+Run from the repo root:  FGS_REFERENCE_TREE=<reference checkout> python tests/golden/make_ref_glue_golden.py
+It rewrites the fixtures in place; `git diff --stat tests/golden` afterwards is the check that the committed fixtures are what the reference's
+glue produces (no change = they are).
 """
 import json
 import sys
@@ -41,7 +43,7 @@ def generate(name: str):
 
 if __name__ == '__main__':
     if not ref_glue.reference_available():
-        sys.exit(f'{ref_glue.REFERENCE_BINDINGS} not found: this script runs in the build container only')
+        sys.exit(f'{ref_glue.REFERENCE_BINDINGS} not found: set FGS_REFERENCE_TREE to a readable checkout of the reference')
     for name in ref_glue.SCENES:
         arrays, trace = generate(name)
         np.savez_compressed(ref_glue.GOLDEN / f'ref_glue_{name}.npz', **arrays)

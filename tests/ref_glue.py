@@ -1,6 +1,6 @@
 """Test infrastructure for the reference-glue pin: ONE scenario, written against the public operator names only, that
-can be run (a) through the reference's own, unmodified torch_bindings/*.py loaded from /root/reference by path (build container only:
-tests/golden/make_ref_glue_golden.py) and (b) through this package's operators, on the CPU simulation or on the MI355X. (a) produces the
+can be run (a) through the reference's own, unmodified torch_bindings/*.py loaded by path from a checkout of the reference named by
+FGS_REFERENCE_TREE (tests/golden/make_ref_glue_golden.py) and (b) through this package's operators, on the CPU simulation or on the MI355X. (a) produces the
 committed fixtures tests/golden/ref_glue_<scene>.npz and the call trace ref_glue_<scene>.trace.json; (b) is compared with them.
 
 What the scenario exercises, with the call shapes of the reference's callers (cited per block): Renderer.py:107-123 (`rasterize` under
@@ -21,6 +21,7 @@ import contextlib
 import importlib.util
 import json
 import math
+import os
 import re
 import sys
 from pathlib import Path
@@ -34,7 +35,8 @@ import helpers
 
 REPO = Path(__file__).resolve().parent.parent
 GOLDEN = REPO / 'tests' / 'golden'
-REFERENCE_BINDINGS = Path('/root/reference/FasterGSCudaBackend/FasterGSCudaBackend/torch_bindings')
+# the reference's Python glue inside its checkout; the checkout is not part of this repository and only the fixture generator reads it
+REFERENCE_BINDINGS = Path(os.environ.get('FGS_REFERENCE_TREE', ''), 'FasterGSCudaBackend', 'FasterGSCudaBackend', 'torch_bindings')
 OP_NAMES = ('diff_rasterize', 'rasterize', 'update_pruning_scores', 'RasterizerSettings', 'FusedAdam', 'update_3d_filter',
             'relocation_adjustment', 'add_noise')
 C_ENTRY_POINTS = ('forward', 'backward', 'inference', 'pruning_scores', 'adam_step', 'update_3d_filter', 'relocation_adjustment', 'add_noise')
@@ -375,7 +377,12 @@ def load_fixture(name: str):
 
 
 def reference_available() -> bool:
-    return (REFERENCE_BINDINGS / 'rasterization.py').exists()
+    if not os.environ.get('FGS_REFERENCE_TREE'):
+        return False
+    try:
+        return (REFERENCE_BINDINGS / 'rasterization.py').is_file()
+    except OSError:      # a tree this user may not read
+        return False
 
 
 if str(REPO / 'tests') not in sys.path:

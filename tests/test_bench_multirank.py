@@ -12,7 +12,7 @@ import pytest
 import helpers
 
 BENCH = str(helpers.REPO / 'bench.py')
-COMMON = ['--sim', '--scene', 'S0', '--n-gaussians', '300', '--steps', '1', '--warmup', '0', '--blocks', '2', '--watchdog', '600']
+COMMON = ['--sim', '--scene', 'S0', '--n-gaussians', '300', '--steps', '1', '--warmup', '0', '--blocks', '2', '--watchdog', '600', '--full']
 
 
 def _run(extra, env=None, timeout=900):

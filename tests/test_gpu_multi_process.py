@@ -120,7 +120,7 @@ def test_bench_two_ranks_sharing_the_device_run_the_multi_rank_branch_on_the_rea
     if not torch.cuda.is_available():
         pytest.skip('no GPU visible')
     cmd = [sys.executable, str(helpers.REPO / 'bench.py'), '--gpus', '2', '--shared-device', '--dp-mode', mode, '--scene', 'S1', '--steps', '3', '--warmup', '1',
-           '--blocks', '2', '--watchdog', '400']
+           '--blocks', '2', '--watchdog', '400', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

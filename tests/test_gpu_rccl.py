@@ -92,7 +92,7 @@ def test_bench_under_torchrun_world1_prints_one_json_line_of_the_single_gpu_iter
         port = s.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', str(port),
            str(helpers.REPO / 'bench.py'), '--gpus', '1', '--scene', 'S0', '--steps', '3', '--warmup', '1', '--blocks', '2', '--no-extras',
-           '--no-cpu-baseline', '--no-pmc']
+           '--no-cpu-baseline', '--no-pmc', '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

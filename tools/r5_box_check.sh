@@ -13,7 +13,7 @@ e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 20
 print(f'd2d copy of 1 GiB: {ms:.3f} ms = {2 * (1 << 30) / ms / 1e6:.0f} GB/s (read + write)')
 PY
-B="python bench.py --no-extras --no-cpu-baseline --no-pmc --blocks 3"
+B="python bench.py --full --no-extras --no-cpu-baseline --no-pmc --blocks 3"
 timeout 100 $B > $O/${T}_product.json 2> $O/${T}_product.err
 FGS_HIP_LIBRARY=$PWD/faster-gaussian-splatting_amd/libfgs_hip_dev.so timeout 100 $B > $O/${T}_dev.json 2> $O/${T}_dev.err
 timeout 100 $B > $O/${T}_product2.json 2> $O/${T}_product2.err
