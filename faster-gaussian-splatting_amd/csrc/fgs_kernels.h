@@ -1,4 +1,4 @@
-// Launch interface between the C-ABI host layer (api.hip) and the gfx950 kernels. One launcher per pipeline stage;
+// Launch interface between the C-ABI host layer (api*.hip, fgs_host.h) and the gfx950 kernels. One launcher per pipeline stage;
 // stage ids K0..K13 refer to SURVEY.md section 2.1.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,6 +78,11 @@ FGS_SWITCH(g_tile_row_group, static_cast<int>(kColumnsTopDown));   // blend_forw
 #ifdef FGS_DEV_SWITCHES
 FGS_SWITCH(g_k11_chain_waves, 4096);                 // blend_backward.hip, option 14: waves of the chained K11 exhibit (variant 5); 4096 = 16 resident waves x 256 CUs
 #endif
+FGS_SWITCH(g_seq_tiles, kSeqTiles);                  // preprocess.hip, option 5: PreprocessArgs::seq_tiles of every K1 launch
+FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
+#ifdef FGS_DEV_SWITCHES
+FGS_SWITCH(g_library_bucket_scan, 0);                // option 11: 1 = rocPRIM scan for K8+K9 and no tile plan (round-2 form, A/B)
+#endif
 FGS_SWITCH(g_plan_experiment, 0);                    // binning.hip, option 12: 1 = blocks unsorted and dealt statically (A/B of the deal itself)
 // radix_sort.hip: stable LSD radix sort of (key, uint32) pairs sized for these two sorts
 FGS_SWITCH(g_depth_sort_mode, 1);                    // option 9 -- bit 0: key range / 9-bit digits, bit 1: 2048-item workgroups (radix_sort.hip)
@@ -132,7 +137,7 @@ struct BlendBackwardArgs {              // K11 (+ per-pixel staging pass)
     uint32_t* live_offsets;                   // [T] first list slot of each tile (planning pass -> stage_pixels_kernel)
     uint32_t n, width, height, grid_w, n_tiles, n_buckets_cap;
     // what the staging pass sets to zero: the hot replicas (clear_hot_f4 16-byte pieces from acc_hot), or -- `clear_everything`, or *dirty_flag != 0 --
-    // records and replicas (clear_all_f4 pieces from acc). K1 cleared the records of the visible Gaussians during the forward pass (api.hip).
+    // records and replicas (clear_all_f4 pieces from acc). K1 cleared the records of the visible Gaussians during the forward pass (api.hip: run_forward).
     uint32_t clear_all_f4, clear_hot_f4; int clear_everything;
     uint32_t* dirty_flag;                 // counters[7]: set by the last kernel of a backward pass over these buffers
     int proper_aa;

@@ -14,7 +14,7 @@ esac
 obj=/tmp/fgs_variant_${name}_${src%.hip}.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -I. -I../../include -Wall -Wno-unused-function $extra "$@" -c $src -o $obj
 objs=""
-for o in api preprocess binning blend_forward blend_backward preprocess_backward selftest loss aux_ops shard_exchange radix_sort densify; do
+for o in $(make -s print-objs); do      # the Makefile's OBJ: every unit of the library, host units included
   if [ "$o.hip" == "$src" ]; then objs="$objs $obj"; else objs="$objs _build/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libfgs_hip_$name.so $objs
