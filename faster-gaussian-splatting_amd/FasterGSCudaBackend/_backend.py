@@ -153,6 +153,27 @@ class Backend:
             return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
         return image
 
+    def inference_aux(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings, to_chw: bool,
+                      clamp_output: bool, alpha: bool = True, depth_expected: bool = True, depth_median: bool = True) -> dict:
+        """fgs_inference_aux: the forward-only render plus the requested per-pixel maps of the same walk, float32 [H,W] (include/fgs_hip.h).
+        Returns {'rgb', 'alpha'?, 'depth'?, 'depth_median'?}; 'rgb' is bit-identical to `inference`."""
+        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
+                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
+        keep: list = []
+        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        shape = (3, settings.height, settings.width) if to_chw else (settings.height, settings.width, 3)
+        out = {'rgb': torch.empty(shape, dtype=torch.float32, device=device)}
+        for name, wanted in (('alpha', alpha), ('depth', depth_expected), ('depth_median', depth_median)):
+            if wanted:
+                out[name] = torch.empty((settings.height, settings.width), dtype=torch.float32, device=device)
+        maps = [out[k].data_ptr() if k in out else None for k in ('alpha', 'depth', 'depth_median')]
+        buffers, cb = self._make_resizer(device, 4)
+        st = _lib.ForwardState()
+        self._check(self.lib.fgs_inference_aux(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
+                                               means.shape[0], C.byref(S), out['rgb'].data_ptr(), int(to_chw), int(clamp_output), *maps, cb, None,
+                                               C.byref(st), _stream_of(device)), 'fgs_inference_aux')
+        return out
+
     def pruning_scores(self, scores, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings) -> None:
         """Accumulates the Speedy-Splat importance scores of one view into `scores` [N] (rasterization.py:159-178)."""
         device = self._check_params((scores, means, scales, rotations, opacities, sh0, sh_rest),

@@ -58,6 +58,7 @@ _SIGNATURES = {
     'fgs_backward': (C.c_int32, [_P] * 2 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P]),
     'fgs_backward_live': (C.c_int32, [_P] * 2 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P]),
     'fgs_inference': (C.c_int32, [_P] * 6 + [_I32, C.POINTER(Settings), _P, _I32, _I32, RESIZE_FN, _P, C.POINTER(ForwardState), _P]),
+    'fgs_inference_aux': (C.c_int32, [_P] * 6 + [_I32, C.POINTER(Settings), _P, _I32, _I32, _P, _P, _P, RESIZE_FN, _P, C.POINTER(ForwardState), _P]),
     'fgs_pruning_scores': (C.c_int32, [_P] * 7 + [_I32, C.POINTER(Settings), RESIZE_FN, _P, C.POINTER(ForwardState), _P]),
     'fgs_adam_step': (C.c_int32, [_P] * 4 + [_I64, _I32, _F64, _F64, _F64, _F64, _P]),
     'fgs_adam_step_multi': (C.c_int32, [_I32] + [C.POINTER(_P)] * 4 + [C.POINTER(_I64), C.POINTER(_I32), C.POINTER(_F64), _F64, _F64, _F64, _P]),

@@ -357,6 +357,33 @@ def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor
                                        rasterizer_settings, to_chw, clamp_output)
 
 
+def rasterize_aux(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                  sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
+                  to_chw: bool, clamp_output: bool = True, alpha: bool = True, depth: 'str | None' = 'expected',
+                  normalize_depth: bool = False) -> dict:
+    """Forward-only render that also returns per-pixel maps of the same blend, float32 [H,W], without gradients:
+      'rgb'          : what `rasterize` returns, bit for bit;
+      'alpha'        : accumulated opacity 1 - T_final (the background is not part of it)            -- alpha=True;
+      'depth'        : sum_i w_i z_i, w_i = T_i alpha_i, z_i = view-space depth of Gaussian i's mean -- depth='expected' or 'both';
+                       normalize_depth=True divides it by alpha.clamp_min(1e-8) (a mean depth; 0 where nothing was blended);
+      'depth_median' : z of the Gaussian that takes T across 0.5, or of the last one blended if the pixel stays more than half
+                       transparent; 0 where nothing was blended                                     -- depth='median' or 'both'."""
+    if depth not in ('expected', 'median', 'both', None):
+        raise ValueError(f"depth must be 'expected', 'median', 'both' or None, not {depth!r}")
+    want_expected, want_median = depth in ('expected', 'both'), depth in ('median', 'both')
+    normalize = normalize_depth and want_expected
+    if not (alpha or want_expected or want_median):
+        raise ValueError('rasterize_aux: no auxiliary map requested (alpha=False, depth=None); use rasterize')
+    _require_gpu(means)
+    out = default_backend().inference_aux(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, rasterizer_settings,
+                                          to_chw, clamp_output, alpha or normalize, want_expected, want_median)
+    if normalize:
+        out['depth'] = out['depth'] / out['alpha'].clamp_min(1e-8)
+        if not alpha:
+            del out['alpha']
+    return out
+
+
 def update_pruning_scores(scores: torch.Tensor, means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor,
                           opacities: torch.Tensor, sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor,
                           rasterizer_settings: RasterizerSettings) -> None:

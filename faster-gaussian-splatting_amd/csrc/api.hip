@@ -79,13 +79,16 @@ StageScope::StageScope(int stage, hipStream_t s) : stream(s) {
 }
 StageScope::~StageScope() { if (idx >= 0) (void)hipEventRecord(g_prof.records[idx].stop, stream); }
 
-// shared by fgs_forward (training), fgs_inference and fgs_pruning_scores
+// shared by fgs_forward (training), fgs_inference, fgs_inference_aux and fgs_pruning_scores
 int run_forward(const ForwardRequest& rq) {
     const bool training = rq.mode == MODE_TRAINING;
     const fgs_settings* settings = rq.settings;
     if (int rc = check_settings(settings)) return rc;
     if (rq.n < 0 || (!rq.image && rq.mode != MODE_SCORES) || (!rq.scores && rq.mode == MODE_SCORES) || !rq.resize || !rq.state_out) return fail(FGS_ERR_INVALID_ARGUMENT, "bad argument (n_primitives=%d)", rq.n);
     if (rq.n > 0 && !rq.params.complete(settings->total_sh_bases_rest)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL parameter tensor");
+    if (rq.aux && rq.mode != MODE_INFERENCE) return fail(FGS_ERR_INVALID_ARGUMENT, "auxiliary maps belong to the inference pass (mode %d)", static_cast<int>(rq.mode));
+    if (rq.aux && !rq.aux_alpha && !rq.aux_depth && !rq.aux_median)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "alpha, depth_expected and depth_median are all NULL: no auxiliary map requested (use fgs_inference)");
     hipStream_t stream = rq.stream;
     const uint32_t n = static_cast<uint32_t>(rq.n);
     const Geometry geo = geometry_of(settings->width, settings->height);
@@ -175,6 +178,11 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
         ba.max_n_processed = tb.max_n_processed; ba.bucket_tile = bb.tile_index; ba.ckpt = bb.ckpt;
     }
     if (rq.mode == MODE_SCORES) { ba.scores = rq.scores; StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_pruning_scores(ba, stream)); }
+    else if (rq.aux) {                                 // the inference blend that also writes the requested maps; z from the means and w2c's depth row
+        ba.means = rq.params.means; ba.w2c = settings->w2c;
+        ba.aux_alpha = rq.aux_alpha; ba.aux_depth = rq.aux_depth; ba.aux_median = rq.aux_median;
+        StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_blend_aux(ba, stream));
+    }
     else { StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_blend(training, ba, stream)); }   // K10 (fwd:239)
     *rq.state_out = fgs_forward_state{static_cast<int32_t>(n_visible), static_cast<int32_t>(n_instances), static_cast<int32_t>(n_buckets_cap), tile_sel};
     return FGS_OK;
@@ -270,6 +278,17 @@ int32_t fgs_inference(const float* means, const float* scales, const float* rota
                       fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream) {
     return run_forward({MODE_INFERENCE, {means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest}, n_primitives, settings,
                         image, to_chw, clamp_output, resize, resize_user, state_out, static_cast<hipStream_t>(stream), nullptr, 0});
+}
+
+int32_t fgs_inference_aux(const float* means, const float* scales, const float* rotations, const float* opacities,
+                          const float* sh_coefficients_0, const float* sh_coefficients_rest, int32_t n_primitives,
+                          const fgs_settings* settings, float* image, int32_t to_chw, int32_t clamp_output,
+                          float* alpha, float* depth_expected, float* depth_median,
+                          fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream) {
+    ForwardRequest rq{MODE_INFERENCE, {means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest}, n_primitives, settings,
+                      image, to_chw, clamp_output, resize, resize_user, state_out, static_cast<hipStream_t>(stream), nullptr, 0};
+    rq.aux = true; rq.aux_alpha = alpha; rq.aux_depth = depth_expected; rq.aux_median = depth_median;
+    return run_forward(rq);
 }
 
 int32_t fgs_pruning_scores(float* scores, const float* means, const float* scales, const float* rotations, const float* opacities,

@@ -119,8 +119,15 @@ __device__ unsigned long long g_k10_timeline[kK10TimelineTiles * 4];
 #ifdef FGS_PAIR_STATS
 __device__ unsigned long long g_k10_pair_stats[8];
 #endif
-template <bool TRAINING>
-__global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
+// AUX (inference only, fgs_inference_aux): the same walk also yields per pixel the accumulated opacity 1 - T, the expected depth sum_i w_i z_i and the
+// median depth (z of the last blended Gaussian met with T > 0.5), z = view_depth of the Gaussian's mean -- the value behind K1's depth key. z takes the
+// seat of the record's hit_mask word in the staged third row, which the blend never reads: it is computed where the record is fetched (the staging and
+// the read-ahead of the next batch alike) and rides to the walk with the colours. Every AUX statement is under `if (AUX)`, and the kernels keep their
+// names: blend_kernel<true> and blend_kernel<false> compile to the instructions they had (the arguments go to the body BY VALUE: by reference the compiler
+// lays the early return out differently), blend_aux_kernel is the third instantiation.
+template <bool TRAINING, bool AUX>
+__device__ __forceinline__ void blend_tile(const BlendArgs a) {
+    static_assert(!(TRAINING && AUX), "the auxiliary maps belong to the inference blend");
     const unsigned tile = tile_of_workgroup(blockIdx.x, a.grid_w, a.n_tiles, a.row_group, a.tile_plan, a.grid_h);
     if (tile >= a.n_tiles) return;
 #ifdef FGS_K10_TIMELINE
@@ -156,6 +163,9 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
     unsigned st_staged = 0, st_pairs = 0, st_mine = 0, st_pass = 0, st_offered = 0;
 #endif
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, T = 1.0f;
+    float depth_sum = 0.0f, depth_med = 0.0f;                          // AUX
+    Camera cam;                                                        // AUX: the third row of w2c is all view_depth reads (wave-uniform scalar loads)
+    if (AUX) { cam.r3[0] = a.w2c[8]; cam.r3[1] = a.w2c[9]; cam.r3[2] = a.w2c[10]; cam.r3[3] = a.w2c[11]; }
     float gate = inside ? kMinAlphaThreshold : __builtin_inff();       // the alpha a pair has to reach to be blended (see the walk below)
     unsigned n_used = 0;
     // "done" (kf:424,477) is not carried as a flag: a pixel is finished exactly when its transmittance has dropped below the threshold
@@ -181,6 +191,7 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
                 const uint32_t prim = a.inst_prims[range.x + batch_start + tid];
                 const float4* r = reinterpret_cast<const float4*>(a.rec + prim);
                 r0 = r[0]; r1 = r[1]; r2 = r[2];
+                if (AUX) { const float* m = a.means + 3 * (size_t)prim; r2.w = view_depth(cam, m[0], m[1], m[2]); }
             }
             s_a[tid] = r0;
             if (TRAINING) {                                                            // kf:430 (inference clamps at store, ki:200)
@@ -201,6 +212,7 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
                 const uint32_t prim = had_ahead ? prim_ahead : a.inst_prims[range.x + next_start + tid];
                 const float4* r = reinterpret_cast<const float4*>(a.rec + prim);
                 n0 = r[0]; n1 = r[1]; n2 = r[2];
+                if (AUX) { const float* m = a.means + 3 * (size_t)prim; n2.w = view_depth(cam, m[0], m[1], m[2]); }
             }
             if (have_ahead && after_start + tid < n_total) prim_ahead = a.inst_prims[range.x + after_start + tid];
         }
@@ -260,6 +272,8 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
                     float4 ha = entry2[0], hb = entry2[kBlendBlock];
                     float blue = entry[2 * kBlendBlock].x, blue2 = entry2[2 * kBlendBlock].x;
                     asm volatile("" : "+v"(gb.z), "+v"(gb.w), "+v"(blue), "+v"(hb.z), "+v"(hb.w), "+v"(blue2), "+v"(ha.x), "+v"(hb.x));
+                    float z = 0.0f, z2 = 0.0f;
+                    if (AUX) { z = entry[2 * kBlendBlock].w; z2 = entry2[2 * kBlendBlock].w; asm volatile("" : "+v"(z), "+v"(z2)); }   // read ahead of the branch like the colours
                     const float dx = ga.x - pxf, dy = ga.y - pyf;
                     const float ex = ha.x - pxf, ey = ha.y - pyf;
                     const float power = -0.5f * (ga.z * dx * dx + gb.x * dy * dy) - ga.w * dx * dy;
@@ -278,6 +292,7 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
                     if (tested >= gate) {
                         const float w = T * alpha;
                         cr += w * gb.z; cg += w * gb.w; cb += w * blue;
+                        if (AUX) { depth_sum += w * z; depth_med = T > 0.5f ? z : depth_med; }   // T before this Gaussian: a select, no mask merge
                         T *= 1.0f - alpha;
                         gate = T < kTransmittanceThreshold ? __builtin_inff() : gate;
                         n_used = batch_start + j0 + k + 1;                             // kf:474
@@ -290,6 +305,7 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
                         if (tested2 >= gate) {
                             const float w = T * alpha2;
                             cr += w * hb.z; cg += w * hb.w; cb += w * blue2;
+                            if (AUX) { depth_sum += w * z2; depth_med = T > 0.5f ? z2 : depth_med; }
                             T *= 1.0f - alpha2;
                             gate = T < kTransmittanceThreshold ? __builtin_inff() : gate;
                             n_used = batch_start + j0 + k2 + 1;
@@ -304,6 +320,11 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
     if (inside) {
         cr += T * a.bg[0]; cg += T * a.bg[1]; cb += T * a.bg[2];                      // kf:483
         const size_t pix = (size_t)a.width * py + px;
+        if (AUX) {                                                                     // image-linear [H,W]; the background is no part of them
+            if (a.aux_alpha != nullptr) a.aux_alpha[pix] = 1.0f - T;
+            if (a.aux_depth != nullptr) a.aux_depth[pix] = depth_sum;
+            if (a.aux_median != nullptr) a.aux_median[pix] = depth_med;
+        }
         const size_t n_pixels = (size_t)a.width * a.height;
         if (TRAINING) {
             a.image[pix] = cr; a.image[n_pixels + pix] = cg; a.image[2 * n_pixels + pix] = cb;
@@ -338,6 +359,10 @@ __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) {
     }
 #endif
 }
+
+template <bool TRAINING>
+__global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) { blend_tile<TRAINING, false>(a); }
+__global__ void __launch_bounds__(kBlendBlock) blend_aux_kernel(const BlendArgs a) { blend_tile<false, true>(a); }
 
 #ifdef FGS_K10_TIMELINE
 }  // namespace fgs
@@ -464,6 +489,13 @@ hipError_t launch_blend(bool training, const BlendArgs& a_in, hipStream_t s) {
     const dim3 grid(blend_grid(a)), block(kBlendBlock);
     if (training) hipLaunchKernelGGL(blend_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(blend_kernel<false>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_aux(const BlendArgs& a_in, hipStream_t s) {
+    BlendArgs a = a_in;
+    if (a.tile_plan == nullptr && (a.row_group == kPlannedBlocks || a.row_group == kBandsThroughPlan)) a.row_group = 0u;
+    hipLaunchKernelGGL(blend_aux_kernel, dim3(blend_grid(a)), dim3(kBlendBlock), 0, s, a);
     return hipGetLastError();
 }
 

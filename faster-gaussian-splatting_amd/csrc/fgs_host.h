@@ -232,13 +232,15 @@ inline void fill_fused_adam(PreprocessBackwardArgs& a, ShRestArgs& sh, const Fus
 }
 
 // ---- the single-GPU pipeline (api.hip); the sharded renderer enters it behind K1 (forward_tail) and ahead of K12 (run_blend_backward) ----
-enum ForwardMode { MODE_TRAINING, MODE_INFERENCE, MODE_SCORES };       // fgs_forward*, fgs_inference, fgs_pruning_scores
+enum ForwardMode { MODE_TRAINING, MODE_INFERENCE, MODE_SCORES };       // fgs_forward*, fgs_inference / fgs_inference_aux, fgs_pruning_scores
 struct ForwardRequest {
     ForwardMode mode; GaussianParams params; int32_t n; const fgs_settings* settings;
     float* image; int to_chw, clamp_output;
     fgs_resize_fn resize; void* user; fgs_forward_state* state_out; hipStream_t stream;
     float* scores;                        // MODE_SCORES: the output, [N]
     int32_t instance_capacity;            // > 0: the host-synchronisation-free form (fgs_forward_async)
+    // MODE_INFERENCE through fgs_inference_aux: per-pixel maps [H,W] written by the blend beside the image (each may be NULL, not all three)
+    bool aux = false; float* aux_alpha = nullptr; float* aux_depth = nullptr; float* aux_median = nullptr;
 };
 // What K2..K10 know of the visible list. on_device: the two counts are BOUNDS (primitive count / caller's instance capacity) and the exact
 // ones stay in the primitive blob's counters. depth_sel >= 0: the list is already depth-sorted and the sorted half is depth_sel.

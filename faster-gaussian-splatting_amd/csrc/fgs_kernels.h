@@ -120,8 +120,12 @@ struct BlendArgs {                      // K10 / inference blend
     uint32_t grid_h;
     int to_chw, clamp_output;
     float* scores;                        // pruning-score mode: accumulated per primitive [N]
+    // auxiliary maps of the inference blend (launch_blend_aux): image-linear [H,W], each may be nullptr; means [N][3] and w2c (row 2 = the depth row) give z
+    const float* means; const float* w2c;
+    float* aux_alpha; float* aux_depth; float* aux_median;
 };
 hipError_t launch_blend(bool training, const BlendArgs& a, hipStream_t s);
+hipError_t launch_blend_aux(const BlendArgs& a, hipStream_t s);       // the inference blend + accumulated opacity / expected depth / median depth
 hipError_t launch_pruning_scores(const BlendArgs& a, hipStream_t s);   // kernels_pruning_scores.cuh:348-505
 
 struct BlendBackwardArgs {              // K11 (+ per-pixel staging pass)

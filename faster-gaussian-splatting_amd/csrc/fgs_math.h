@@ -198,6 +198,7 @@ struct Projection {
 };
 
 __device__ __forceinline__ float view_depth(const Camera& cam, float mx, float my, float mz) {
+#pragma clang fp contract(off)      // the bits of this value are K1's depth key: the same in a unit built with FMA contraction (blend_forward.hip)
     return cam.r3[0] * mx + cam.r3[1] * my + cam.r3[2] * mz + cam.r3[3];
 }
 

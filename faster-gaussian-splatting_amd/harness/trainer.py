@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, rasterize
+from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, rasterize, rasterize_aux
 
 from .scenes import View
 
@@ -77,6 +77,14 @@ def render_image_benchmark(g: Gaussians, view: View, to_chw: bool = True) -> tor
     """Renderer.py:107-123."""
     return rasterize(*g.tensors(), rasterizer_settings=extract_settings(view, g.active_sh_bases, view.background_color),
                      to_chw=to_chw, clamp_output=True)
+
+
+@torch.inference_mode()
+def render_image_aux(g: Gaussians, view: View, to_chw: bool = True, alpha: bool = True, depth: 'str | None' = 'expected',
+                     normalize_depth: bool = False) -> dict:
+    """render_image_benchmark plus the accumulated-opacity and depth maps of the same blend (rasterize_aux): {'rgb', 'alpha', 'depth', 'depth_median'}."""
+    return rasterize_aux(*g.tensors(), rasterizer_settings=extract_settings(view, g.active_sh_bases, view.background_color),
+                         to_chw=to_chw, clamp_output=True, alpha=alpha, depth=depth, normalize_depth=normalize_depth)
 
 
 def l1_loss(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

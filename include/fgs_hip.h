@@ -125,6 +125,21 @@ int32_t fgs_inference(const float* means, const float* scales, const float* rota
                       const fgs_settings* settings, float* image, int32_t to_chw, int32_t clamp_output,
                       fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream);
 
+/* fgs_inference that also returns per-pixel maps of the same walk, fp32 [H,W] image-linear, each optional (NULL = not wanted; all three NULL is
+ * FGS_ERR_INVALID_ARGUMENT). They come from exactly the (pixel, Gaussian) pairs the colour blends -- same sub-tile cull, alpha >= 1/255, stop once
+ * T < 1e-4 -- with w_i = T_before_i * alpha_i and z_i the view-space depth of Gaussian i's mean (row 2 of w2c applied to it: the depth key's value):
+ *   alpha          = 1 - T_final                  (the background is not part of it)
+ *   depth_expected = sum_i w_i z_i                (not normalised; divide by alpha for a mean depth; 0 where nothing was blended)
+ *   depth_median   = z of the last blended Gaussian whose T_before_i > 0.5: the one that carries T across 0.5 where the pixel becomes more than
+ *                    half opaque, otherwise the last one blended; 0 where nothing was blended.
+ * `image` is bit-identical to fgs_inference's. The maps carry no gradient. Same buffers, same single host read, everything on `stream`.
+ * n_primitives == 0: image = background, all maps 0. */
+int32_t fgs_inference_aux(const float* means, const float* scales, const float* rotations, const float* opacities,
+                          const float* sh_coefficients_0, const float* sh_coefficients_rest, int32_t n_primitives,
+                          const fgs_settings* settings, float* image, int32_t to_chw, int32_t clamp_output,
+                          float* alpha, float* depth_expected, float* depth_median,
+                          fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream);
+
 /* replaces _C.pruning_scores (rasterization_api.cu:250-309 -> rasterization/src/pruning_scores.cu):
  * accumulates the Speedy-Splat importance score of every primitive for one view into scores[N]. */
 int32_t fgs_pruning_scores(float* scores, const float* means, const float* scales, const float* rotations, const float* opacities,
