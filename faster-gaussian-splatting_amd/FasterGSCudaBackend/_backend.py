@@ -40,6 +40,14 @@ class ForwardResult(NamedTuple):
     state: tuple            # (n_visible, n_instances, n_buckets, selector), opaque
 
 
+class ForwardAuxResult(NamedTuple):
+    image: torch.Tensor
+    alpha: Optional[torch.Tensor]   # [H,W] accumulated opacity 1 - T_final, or None if not requested
+    depth: Optional[torch.Tensor]   # [H,W] expected depth sum_i w_i z_i (not normalised), or None
+    buffers: tuple
+    state: tuple
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None or t.numel() == 0 else t.data_ptr()
 
@@ -117,6 +125,27 @@ class Backend:
                                                    means.shape[0], C.byref(S), image.data_ptr(), int(instance_capacity), cb, None, C.byref(st),
                                                    _stream_of(device)), 'fgs_forward_async')
         return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
+
+    def forward_aux(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings, alpha: bool = True,
+                    depth: bool = True, instance_capacity: int | None = None) -> ForwardAuxResult:
+        """fgs_forward_aux: the training forward pass plus accumulated opacity and / or expected depth [H,W] of the same walk, and the depth
+        checkpoints `backward_aux` needs. The buffers are valid input to the plain `backward` / `backward_adam_fused` too."""
+        if instance_capacity is not None:
+            raise RuntimeError('forward_aux: the asynchronous forward pass (instance_capacity) does not return maps; use forward() or drop the capacity')
+        if not (alpha or depth):
+            raise RuntimeError('forward_aux: neither alpha nor depth requested (use forward)')
+        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
+                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
+        keep: list = []
+        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        image = torch.empty((3, settings.height, settings.width), dtype=torch.float32, device=device)
+        maps = [torch.empty((settings.height, settings.width), dtype=torch.float32, device=device) if wanted else None for wanted in (alpha, depth)]
+        buffers, cb = self._make_resizer(device, 4)
+        st = _lib.ForwardState()
+        self._check(self.lib.fgs_forward_aux(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
+                                             means.shape[0], C.byref(S), image.data_ptr(), *[m.data_ptr() if m is not None else None for m in maps],
+                                             cb, None, C.byref(st), _stream_of(device)), 'fgs_forward_aux')
+        return ForwardAuxResult(image, maps[0], maps[1], tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
 
     def forward_counts(self, result: ForwardResult, n_primitives: int):
         """Enqueues the read-back of (n_visible, n_instances, capacity_exceeded) of a forward pass; returns (pinned int32[3] tensor, event).
@@ -226,9 +255,60 @@ class Backend:
                     'fgs_backward')
         return grads
 
+    def backward_aux(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
+                     buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None) -> tuple:
+        """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero; both None is `backward`
+        exactly). `depth` is the expected-depth map the forward pass returned (needed with grad_depth)."""
+        if grad_alpha is None and grad_depth is None:
+            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state, out, live_blocks)
+        device = self._check_params((means, scales, rotations, opacities, sh_rest), ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest'))
+        keep: list = []
+        n = means.shape[0]
+        total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
+        S = self._settings(settings, total_rest, device, keep)
+        hw = (int(settings.height), int(settings.width))
+        grad_image = grad_image.to(dtype=torch.float32).contiguous()
+        for name, t in (('grad_alpha', grad_alpha), ('grad_depth', grad_depth), ('depth', depth if grad_depth is not None else None)):
+            if t is not None and (tuple(t.shape) != hw or t.device != device):
+                raise RuntimeError(f'{name} must be a [H,W] = {hw} tensor on the parameters\' device')
+        if grad_depth is not None and depth is None:
+            raise RuntimeError('backward_aux: grad_depth needs the expected-depth map of forward_aux')
+        grad_alpha = grad_alpha.to(dtype=torch.float32).contiguous() if grad_alpha is not None else None
+        grad_depth = grad_depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
+        depth = depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
+        shapes = ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3))
+        if out is None:
+            grads = tuple(torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes)
+        else:
+            grads = tuple(out)
+            for g, sh in zip(grads, shapes):
+                if tuple(g.shape) != sh or g.dtype != torch.float32 or not g.is_contiguous() or g.device != device:
+                    raise RuntimeError(f'preallocated gradient has shape {tuple(g.shape)}, expected contiguous float32 {sh}')
+        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
+        if dens is not None and (dens.dtype != torch.float32 or not dens.is_contiguous() or dens.device != device or dens.numel() != 2 * n):
+            raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
+        if live_blocks is not None and (live_blocks.dtype != torch.uint8 or live_blocks.device != device or not live_blocks.is_contiguous()
+                                        or live_blocks.numel() != (n + 63) // 64):
+            raise RuntimeError('live_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
+        scratch = self._scratch_aux(n, settings, device)
+        st = _lib.ForwardState(*state)
+        self._check(self.lib.fgs_backward_aux(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
+                                              _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
+                                              _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
+                                              _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _stream_of(device)),
+                    'fgs_backward_aux')
+        return grads
+
+    def _scratch_aux(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
+        nbytes = int(self.lib.fgs_backward_aux_scratch_bytes(n, int(settings.width), int(settings.height)))
+        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
-                            buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15) -> None:
+                            buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,
+                            grad_alpha=None, grad_depth=None) -> None:
         """params / moments / lrs in optimizer-group order: means, sh0, sh_rest, opacities, scales, rotations (Model.py:238-245)."""
+        if grad_alpha is not None or grad_depth is not None:
+            raise RuntimeError('backward_adam_fused takes no alpha / depth gradients: use backward_aux and an optimizer step of its own')
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         keep: list = []
         n = params[0].shape[0]
@@ -361,8 +441,10 @@ class Backend:
         return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
 
     def backward_to_records(self, grad_image, image, buffers, settings: RasterizerSettings, state, total_sh_rest: int,
-                            out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None) -> torch.Tensor:
+                            out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None) -> torch.Tensor:
         """K11 of a view rendered by `forward_from_records` -> float32 [n_records, 9] accumulator records."""
+        if grad_alpha is not None or grad_depth is not None:
+            raise RuntimeError('backward_to_records takes no alpha / depth gradients: the sharded and record paths render colour only')
         device = image.device
         n = int(state[0])
         keep: list = []

@@ -348,6 +348,56 @@ def diff_rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.T
                             rasterizer_settings)
 
 
+class _RasterizeAux(torch.autograd.Function):
+    """_Rasterize that also returns accumulated opacity and expected depth, differentiable like the image (fgs_forward_aux / fgs_backward_aux).
+    Always the synchronous forward pass; gradients in fresh tensors (no arena, no live-block hand-over: an optimizer reads them all)."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                rasterizer_settings: RasterizerSettings, alpha: bool, depth: bool):
+        _require_gpu(means)
+        res = default_backend().forward_aux(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, rasterizer_settings, alpha, depth)
+        ctx.rasterizer_settings = rasterizer_settings
+        ctx.buffer_state = res.state
+        ctx.has_depth = res.depth is not None
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None (= zero), not as a tensor of zeros
+        shape = (rasterizer_settings.height, rasterizer_settings.width)
+        a = res.alpha if res.alpha is not None else means.new_empty(shape)            # autograd wants tensors: the placeholders are non-differentiable
+        d = res.depth if res.depth is not None else means.new_empty(shape)
+        ctx.save_for_backward(res.image, d, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.mark_non_differentiable(densification_info, *([a] if res.alpha is None else []), *([d] if res.depth is None else []))
+        return res.image, a, d
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_alpha, grad_depth):
+        image, depth, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        if not ctx.has_depth:
+            grad_depth = None
+        clear_live_blocks([means])
+        grads = default_backend().backward_aux(ctx.densification_info, grad_image.contiguous(),
+                                               grad_alpha.contiguous() if grad_alpha is not None else None,
+                                               grad_depth.contiguous() if grad_depth is not None else None,
+                                               image, depth, means, scales, rotations, opacities, sh_rest, buffers, ctx.rasterizer_settings, ctx.buffer_state)
+        return (*grads, None, None, None, None)
+
+
+def diff_rasterize_aux(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                       sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                       rasterizer_settings: RasterizerSettings, alpha: bool = True, depth: bool = True):
+    """Training render that also returns, differentiable, the accumulated opacity A = 1 - T_final and the expected depth D = sum_i w_i z_i
+    (w_i = T_i alpha_i, z_i = view-space depth of Gaussian i's mean; not normalised: D / A.clamp_min(1e-8) is a mean depth and autograd handles the
+    division). Returns (image [3,H,W], alpha [H,W] or None, depth [H,W] or None). The median depth stays inference-only (rasterize_aux)."""
+    if not (alpha or depth):
+        raise ValueError('diff_rasterize_aux: neither alpha nor depth requested; use diff_rasterize')
+    image, a, d = _RasterizeAux.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                                      rasterizer_settings, bool(alpha), bool(depth))
+    return image, (a if alpha else None), (d if depth else None)
+
+
 def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
               sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
               to_chw: bool, clamp_output: bool = True) -> torch.Tensor:

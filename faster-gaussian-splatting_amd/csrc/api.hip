@@ -86,7 +86,11 @@ int run_forward(const ForwardRequest& rq) {
     if (int rc = check_settings(settings)) return rc;
     if (rq.n < 0 || (!rq.image && rq.mode != MODE_SCORES) || (!rq.scores && rq.mode == MODE_SCORES) || !rq.resize || !rq.state_out) return fail(FGS_ERR_INVALID_ARGUMENT, "bad argument (n_primitives=%d)", rq.n);
     if (rq.n > 0 && !rq.params.complete(settings->total_sh_bases_rest)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL parameter tensor");
-    if (rq.aux && rq.mode != MODE_INFERENCE) return fail(FGS_ERR_INVALID_ARGUMENT, "auxiliary maps belong to the inference pass (mode %d)", static_cast<int>(rq.mode));
+    if (rq.aux && rq.mode == MODE_SCORES) return fail(FGS_ERR_INVALID_ARGUMENT, "auxiliary maps belong to the inference and training passes (mode %d)", static_cast<int>(rq.mode));
+    if (rq.aux && training && (rq.instance_capacity > 0 || rq.aux_median))
+        return fail(FGS_ERR_INVALID_ARGUMENT, "the training pass returns alpha and depth_expected through fgs_forward_aux only: no median depth, no asynchronous form");
+    if (rq.aux && training && !rq.aux_alpha && !rq.aux_depth)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "alpha and depth_expected are both NULL: no auxiliary map requested (use fgs_forward)");
     if (rq.aux && !rq.aux_alpha && !rq.aux_depth && !rq.aux_median)
         return fail(FGS_ERR_INVALID_ARGUMENT, "alpha, depth_expected and depth_median are all NULL: no auxiliary map requested (use fgs_inference)");
     hipStream_t stream = rq.stream;
@@ -169,15 +173,21 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
             ba.tile_plan = need_plan ? tb.tile_plan : nullptr;
         }
     }
+    BucketBuffers bb{};
     if (training) {
         // the bucket buffer sized by its bound (no read-back of n_buckets, fwd:234)
         n_buckets_cap = bucket_capacity(n_instances, geo.n_tiles);
-        BucketBuffers bb;
-        if (int rc = acquire(bb, rq.resize, rq.user, FGS_BUF_BUCKET, n_buckets_cap)) return rc;
+        if (int rc = acquire(bb, rq.resize, rq.user, FGS_BUF_BUCKET, n_buckets_cap, rq.aux)) return rc;
         ba.bucket_offsets = tb.bucket_offsets; ba.final_T = tb.final_T; ba.n_processed = tb.n_processed;
         ba.max_n_processed = tb.max_n_processed; ba.bucket_tile = bb.tile_index; ba.ckpt = bb.ckpt;
     }
     if (rq.mode == MODE_SCORES) { ba.scores = rq.scores; StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_pruning_scores(ba, stream)); }
+    else if (rq.aux && training) {                     // the training blend that also writes alpha / expected depth and the depth checkpoints
+        ba.means = rq.params.means; ba.w2c = settings->w2c; ba.aux_alpha = rq.aux_alpha; ba.aux_depth = rq.aux_depth;
+        StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_blend_training_aux(BlendDepthArgs{ba, bb.ckpt_d}, stream));
+        *rq.state_out = fgs_forward_state{static_cast<int32_t>(n_visible), static_cast<int32_t>(n_instances), static_cast<int32_t>(n_buckets_cap), tile_sel | kStateDepthCheckpoints};
+        return FGS_OK;
+    }
     else if (rq.aux) {                                 // the inference blend that also writes the requested maps; z from the means and w2c's depth row
         ba.means = rq.params.means; ba.w2c = settings->w2c;
         ba.aux_alpha = rq.aux_alpha; ba.aux_depth = rq.aux_depth; ba.aux_median = rq.aux_median;
@@ -188,7 +198,7 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
     return FGS_OK;
 }
 
-int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state) {
+int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth) {
     if (int rc = check_settings(settings)) return rc;
     if (!state || n_primitives < 0) return fail(FGS_ERR_INVALID_ARGUMENT, "bad state / n_primitives");
     if (static_cast<uint64_t>(n_primitives) * kAccRecordWords + PrimitiveBuffers::kHotFloats > 0xfffffff0ull)      // K11 addresses the accumulator records by 32-bit float offsets
@@ -201,12 +211,12 @@ int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primiti
     P.pb = PrimitiveBuffers::carve(pc, static_cast<uint32_t>(n_primitives));
     P.tb = TileBuffers::carve(tc, P.geo.n_tiles, true);
     P.ib = InstanceBuffers::carve(ic, static_cast<uint32_t>(state->n_instances), P.geo.key_bytes, P.geo.end_bit);
-    P.bb = BucketBuffers::carve(bc, static_cast<uint32_t>(state->n_buckets));
-    P.sc = BackwardScratch::carve(sc, static_cast<uint32_t>(n_primitives), P.geo.n_tiles);
+    P.bb = BucketBuffers::carve(bc, static_cast<uint32_t>(state->n_buckets), (state->selector & kStateDepthCheckpoints) != 0);
+    P.sc = BackwardScratch::carve(sc, static_cast<uint32_t>(n_primitives), P.geo.n_tiles, with_depth);
     return FGS_OK;
 }
 
-int run_blend_backward(const BackwardPlan& P, const float* grad_image, const float* image, hipStream_t stream, bool cleared_by_preprocess) {
+static BlendBackwardArgs blend_backward_args(const BackwardPlan& P, const float* grad_image, const float* image, bool cleared_by_preprocess) {
     BlendBackwardArgs a{};
     // replaces api:127-134. K11 adds into 9-float records that must start at zero. The records of the visible Gaussians were cleared by K1 during the
     // forward pass (PrimitiveBuffers::acc); what is left for the staging kernel is the hot replicas (9 MB) -- or everything, when no K1 of this
@@ -218,7 +228,7 @@ int run_blend_backward(const BackwardPlan& P, const float* grad_image, const flo
     a.clear_hot_f4 = P.n > 0 ? static_cast<uint32_t>(PrimitiveBuffers::kHotFloats / 4) : 0u;
     a.clear_everything = cleared_by_preprocess ? 0 : 1;
     a.dirty_flag = P.pb.counters + 7;
-    a.ranges = P.tb.ranges; a.bucket_offsets = P.tb.bucket_offsets; a.inst_prims = P.ib.prims[P.state->selector]; a.rec = P.pb.rec;
+    a.ranges = P.tb.ranges; a.bucket_offsets = P.tb.bucket_offsets; a.inst_prims = P.ib.prims[P.state->selector & 1]; a.rec = P.pb.rec;
     a.bg = P.settings->bg_color; a.grad_image = grad_image; a.image = image;
     a.final_T = P.tb.final_T; a.n_processed = P.tb.n_processed; a.max_n_processed = P.tb.max_n_processed;
     a.bucket_tile = P.bb.tile_index; a.ckpt = P.bb.ckpt; a.pixrec = P.sc.pixrec; a.acc = P.pb.acc;
@@ -228,8 +238,27 @@ int run_blend_backward(const BackwardPlan& P, const float* grad_image, const flo
     a.grid_w = P.geo.grid_w; a.n_tiles = P.geo.n_tiles; a.n_buckets_cap = static_cast<uint32_t>(P.state->n_buckets);
     a.proper_aa = P.settings->proper_antialiasing ? 1 : 0;
     a.variant = blend_backward_variant();           // once per pass: the planning pass and the kernel see the same formulation
+    return a;
+}
+
+int run_blend_backward(const BackwardPlan& P, const float* grad_image, const float* image, hipStream_t stream, bool cleared_by_preprocess) {
+    const BlendBackwardArgs a = blend_backward_args(P, grad_image, image, cleared_by_preprocess);
     { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels(a, stream)); }
     { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward(a, stream)); }     // K11 (bwd:56)
+    return FGS_OK;
+}
+
+int run_blend_backward_aux(const BackwardPlan& P, const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth,
+                           const float* depth, const float* means, hipStream_t stream) {
+    BlendBackwardDepthArgs a{};
+    a.blend = blend_backward_args(P, grad_image, image, true);
+    a.d.grad_alpha = grad_alpha; a.d.grad_depth = grad_depth; a.d.depth = depth;
+    a.d.ckpt_d = grad_depth ? P.bb.ckpt_d : nullptr;
+    a.d.pixaux = P.sc.pixaux; a.d.means = means; a.d.w2c = P.settings->w2c;
+    a.d.acc_z = P.sc.acc_z; a.d.acc_z_hot = P.sc.acc_z_hot;
+    a.d.clear_z_f4 = static_cast<uint32_t>(static_cast<size_t>(reinterpret_cast<char*>(P.sc.acc_z_hot + BackwardScratch::kHotDepthFloats) - reinterpret_cast<char*>(P.sc.acc_z)) / 16);
+    { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels_depth(a, stream)); }
+    { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward_depth(a, stream)); }
     return FGS_OK;
 }
 }  // namespace fgs
@@ -250,6 +279,16 @@ int32_t fgs_forward(const float* means, const float* scales, const float* rotati
                     fgs_forward_state* state_out, void* stream) {
     return run_forward({MODE_TRAINING, {means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest}, n_primitives, settings,
                         image, 1, 0, resize, resize_user, state_out, static_cast<hipStream_t>(stream), nullptr, 0});
+}
+
+int32_t fgs_forward_aux(const float* means, const float* scales, const float* rotations, const float* opacities,
+                        const float* sh_coefficients_0, const float* sh_coefficients_rest, int32_t n_primitives,
+                        const fgs_settings* settings, float* image, float* alpha, float* depth_expected,
+                        fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream) {
+    ForwardRequest rq{MODE_TRAINING, {means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest}, n_primitives, settings,
+                      image, 1, 0, resize, resize_user, state_out, static_cast<hipStream_t>(stream), nullptr, 0};
+    rq.aux = true; rq.aux_alpha = alpha; rq.aux_depth = depth_expected;
+    return run_forward(rq);
 }
 
 int32_t fgs_forward_async(const float* means, const float* scales, const float* rotations, const float* opacities,
@@ -305,6 +344,13 @@ size_t fgs_backward_scratch_bytes(int32_t n_primitives, int32_t width, int32_t h
     return c.total();
 }
 
+size_t fgs_backward_aux_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height) {
+    if (n_primitives < 0 || width <= 0 || height <= 0) return 0;
+    Carver c(nullptr);
+    BackwardScratch::carve(c, static_cast<uint32_t>(n_primitives), geometry_of(width, height).n_tiles, true);
+    return c.total();
+}
+
 int32_t fgs_backward_live(const float* grad_image, const float* image,
                           const float* means, const float* scales, const float* rotations, const float* opacities,
                           const float* sh_coefficients_rest,
@@ -313,14 +359,33 @@ int32_t fgs_backward_live(const float* grad_image, const float* image,
                           float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
                           float* densification_info, void* scratch,
                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream_) {
+    return fgs_backward_aux(grad_image, image, nullptr, nullptr, nullptr, means, scales, rotations, opacities, sh_coefficients_rest, primitive_buffers,
+                            tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities, grad_sh_coefficients_0,
+                            grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks, stream_);
+}
+
+// K11 and K12 of the single-GPU path. Without map gradients this IS fgs_backward_live: the plain staging pass and K11, the plain scratch layout.
+int32_t fgs_backward_aux(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                         const float* means, const float* scales, const float* rotations, const float* opacities,
+                         const float* sh_coefficients_rest,
+                         void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                         float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                         float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                         float* densification_info, void* scratch,
+                         int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream_) {
+    const bool with_maps = grad_alpha != nullptr || grad_depth != nullptr;
     BackwardPlan P;
-    if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state)) return rc;
+    if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state, with_maps)) return rc;
     if (!grad_image || !image) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL image / grad_image");
+    if (grad_depth && !(state->selector & kStateDepthCheckpoints))
+        return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth needs the depth checkpoints that fgs_forward_aux writes: these buffers were filled by a forward pass without them");
+    if (grad_depth && !depth_expected) return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth without depth_expected (the map fgs_forward_aux returned)");
     if (n_primitives == 0) return FGS_OK;
     if (!means || !scales || !rotations || !opacities || !grad_means || !grad_scales || !grad_rotations || !grad_opacities || !grad_sh_coefficients_0)
         return fail(FGS_ERR_INVALID_ARGUMENT, "NULL parameter / gradient tensor");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (int rc = run_blend_backward(P, grad_image, image, stream)) return rc;
+    if (with_maps) { if (int rc = run_blend_backward_aux(P, grad_image, image, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
+    else if (int rc = run_blend_backward(P, grad_image, image, stream)) return rc;
 
     PreprocessBackwardArgs a{};
     ShRestArgs sh{};
@@ -334,11 +399,13 @@ int32_t fgs_backward_live(const float* grad_image, const float* image,
         StageScope t(ST_PREPROCESS_BACKWARD, stream);
         a.live_blocks = live_blocks;
         FGS_HIP(launch_backward_gradients(a, sh, stream));
-        return FGS_OK;
+    } else {
+        if (live_blocks != nullptr) FGS_HIP(hipMemsetAsync(live_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // A/B form: no flags, every block "live"
+        { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_preprocess_backward(false, a, stream)); }   // round-1 form: geometry kernel + SH-rest kernel
+        if (settings->total_sh_bases_rest > 0) { StageScope t(ST_SH_REST_BACKWARD, stream); FGS_HIP(launch_sh_rest_backward(false, sh, stream)); }
     }
-    if (live_blocks != nullptr) FGS_HIP(hipMemsetAsync(live_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // A/B form: no flags, every block "live"
-    { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_preprocess_backward(false, a, stream)); }   // round-1 form: geometry kernel + SH-rest kernel
-    if (settings->total_sh_bases_rest > 0) { StageScope t(ST_SH_REST_BACKWARD, stream); FGS_HIP(launch_sh_rest_backward(false, sh, stream)); }
+    // z_i's own dependence on mean_i: grad_means += dL/dz w2c[2, 0:3], after K12 has written every element. Not launched without a depth gradient.
+    if (grad_depth) { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_depth_mean_gradient(P.sc.acc_z, P.pb.n_touched, settings->w2c, grad_means, static_cast<uint32_t>(n_primitives), stream)); }
     return FGS_OK;
 }
 

@@ -26,7 +26,18 @@
 namespace fgs {
 
 // staging pass: kb:349-380 hoisted out of the per-bucket loop
-__global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BlendBackwardArgs a) {
+// DEPTH (stage_pixels_kernel<true>, fgs_backward_aux): additionally stages (gD, gA, D_final, T_final) per pixel -- the upstream gradients of expected
+// depth and accumulated opacity and what K11 needs to enlarge the remaining-colour scalar by gD (D_final - D_ckpt) + gA (T_ckpt - T_final) -- and
+// clears acc_z and its hot replicas. Every DEPTH statement is under `if constexpr`: stage_pixels_kernel<false> compiles to the instructions the kernel had.
+template <bool DEPTH> using BackwardArgsOf = std::conditional_t<DEPTH, BlendBackwardDepthArgs, BlendBackwardArgs>;
+__device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardArgs& v) { return v; }
+__device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardDepthArgs& v) { return v.blend; }
+__device__ __forceinline__ BlendDepthPart depth_part(const BlendBackwardArgs&) { return BlendDepthPart{}; }          // never read: every use is under `if constexpr (DEPTH)`
+__device__ __forceinline__ const BlendDepthPart& depth_part(const BlendBackwardDepthArgs& v) { return v.d; }
+template <bool DEPTH>
+__global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BackwardArgsOf<DEPTH> args) {
+    const BlendBackwardArgs& a = blend_part(args);
+    [[maybe_unused]] const BlendDepthPart& x = depth_part(args);       // DEPTH only
     // (Round 6, measured and withdrawn: XCD x taking a contiguous band of tiles, so that the two tiles sharing a 128-byte line of the six image planes
     // run under one L2 -- what took 6 % off the loss kernels -- leaves this kernel at 0.040 ms: profiles/r06_ab_stage_pixels_xcd.txt.)
     const unsigned tile = blockIdx.x;
@@ -35,6 +46,7 @@ __global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BlendBa
         const unsigned tile_x = tile % a.grid_w, tile_y = tile / a.grid_w;
         const unsigned px = tile_x * kTileW + (local % kTileW), py = tile_y * kTileH + (local / kTileW);
         float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+        [[maybe_unused]] float4 e = make_float4(0.0f, 0.0f, 0.0f, 0.0f);                       // DEPTH: gD, gA, D_final, T_final
         if (px < a.width && py < a.height) {
             const size_t pix = (size_t)a.width * py + px, n_pixels = (size_t)a.width * a.height;
             const float fT = a.final_T[(size_t)tile * kTilePixels + local];
@@ -43,9 +55,15 @@ __global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BlendBa
             g.w = fT * -(g.x * b0 + g.y * b1 + g.z * b2);                                  // kb:375-377
             c.x = a.image[pix] - fT * b0; c.y = a.image[n_pixels + pix] - fT * b1; c.z = a.image[2 * n_pixels + pix] - fT * b2;
             c.w = __uint_as_float(a.n_processed[(size_t)tile * kTilePixels + local]);
+            if constexpr (DEPTH) {
+                e.w = fT;
+                if (x.grad_alpha != nullptr) e.y = x.grad_alpha[pix];
+                if (x.grad_depth != nullptr) { e.x = x.grad_depth[pix]; e.z = x.depth[pix]; }
+            }
         }
         a.pixrec[((size_t)tile * kTilePixels + local) * 2] = g;
         a.pixrec[((size_t)tile * kTilePixels + local) * 2 + 1] = c;
+        if constexpr (DEPTH) x.pixaux[(size_t)tile * kTilePixels + local] = e;
         // the tile's entries of the live-bucket list (variant 3): the planning pass has scanned the per-tile counts, the entries are written here,
         // by 12 k workgroups instead of one
         if (a.live_offsets != nullptr) {
@@ -64,6 +82,12 @@ __global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BlendBa
         float4* const z = reinterpret_cast<float4*>(everything ? a.acc : a.acc_hot);
         const unsigned per_group = (n_f4 + gridDim.x - 1u) / gridDim.x;
         const unsigned first = tile * per_group, last = min(first + per_group, n_f4);
+        for (unsigned k = first + local; k < last; k += kTilePixels) z[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if constexpr (DEPTH) {       // acc_z and its replicas start every depth pass at zero: K1 does not know of them
+        float4* const z = reinterpret_cast<float4*>(x.acc_z);
+        const unsigned per_group = (x.clear_z_f4 + gridDim.x - 1u) / gridDim.x;
+        const unsigned first = tile * per_group, last = min(first + per_group, x.clear_z_f4);
         for (unsigned k = first + local; k < last; k += kTilePixels) z[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
@@ -402,7 +426,17 @@ __device__ unsigned long long g_k11_pair_stats[8];
 #define FGS_K11_WAVES_PER_GROUP 1
 #endif
 constexpr unsigned kCompactWaves = FGS_K11_WAVES_PER_GROUP;      // independent waves (one work item each, no barrier) per workgroup
-__global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_kernel(const BlendBackwardArgs a) {
+// DEPTH (blend_backward_compact_kernel<true>, fgs_backward_aux): alpha and expected depth are two more channels of the blend (per-Gaussian value 1
+// resp. z, background 0), and the walk is linear in (channel value x upstream gradient): the per-pair dot becomes cg = c . gC + z gD + gA, the
+// injected scalar was enlarged by the staging above, and dL/dalpha -- with it the eight geometry sums -- picks both up unchanged. One new sum,
+// a_z = sum w gD = dL/dz, leaves through one float atomic per lane into acc_z (hot Gaussians: into the tile's replica, like their records).
+// gD and gA ride in the pixel-centre ring, which becomes a 16-byte ring (x, y, gD, gA) read with one ds_read_b128 like the dL/dC ring:
+// [xy ring 4 KB | inj 1.5 KB | pix ring 4 KB] = 9 728 bytes per wave = eight allocation granules instead of six. Every DEPTH
+// statement is under `if constexpr`, and `a` is the kernel argument itself: blend_backward_compact_kernel<false> compiles to the instructions the kernel had.
+template <bool DEPTH>
+__global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_kernel(const BackwardArgsOf<DEPTH> args) {
+    const BlendBackwardArgs& a = blend_part(args);
+    [[maybe_unused]] const BlendDepthPart& x = depth_part(args);       // DEPTH only
     const unsigned lane = threadIdx.x & 63u, wave_in_group = threadIdx.x >> 6;
     // Per live pixel: (dL/dC rgb, rel_last as a float) in s_pix and the pixel centre (x, y) in s_xy; slot n_px = dead sentinel (rel 0).
     // Until here x | y << 8 | rel << 16 were packed in the fourth float: three v_cvt_f32_ubyte (4.3 cycles each, tools/valu_rate.hip) and two
@@ -419,7 +453,8 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
     // address IS the ring offset (no base to add): [xy ring 2 KB | inj 1.5 KB | pix ring 4 KB] = 7 680 bytes = six LDS allocation granules
     // (1 280 bytes on this part: with 8 KB the timeline showed 17 waves per CU in flight, with 6.7 KB before the ring 19).
     constexpr unsigned kRing = 256;
-    constexpr unsigned kXyBytes = kRing * 8u, kInjBytes = kTilePixels * 8u, kPixBytes = kRing * 16u, kPixBase = kXyBytes + kInjBytes;
+    constexpr unsigned kXySlot = DEPTH ? 16u : 8u;
+    constexpr unsigned kXyBytes = kRing * kXySlot, kInjBytes = kTilePixels * 8u, kPixBytes = kRing * 16u, kPixBase = kXyBytes + kInjBytes;
     static_assert(kPixBase % 16u == 0, "the 16-byte ring is 16-byte aligned");
     __shared__ __attribute__((aligned(16))) char s_block[kCompactWaves][kXyBytes + kInjBytes + kPixBytes];
     char* const s_base = s_block[wave_in_group];
@@ -434,6 +469,8 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
     const unsigned n_live = *a.live_count;
     const float lane_f = static_cast<float>(lane);
     const bool lane0 = lane == 0;
+    [[maybe_unused]] Camera cam;                                   // DEPTH: the depth row of w2c (wave-uniform scalar loads)
+    if constexpr (DEPTH) { cam.r3[0] = x.w2c[8]; cam.r3[1] = x.w2c[9]; cam.r3[2] = x.w2c[10]; cam.r3[3] = x.w2c[11]; }
     // (round 6, measured and withdrawn: XCD x walking a contiguous eighth of the live list, so that the buckets of neighbouring tiles share an L2 --
     // K11 0.313 -> 0.319 ms at S2, layered scene 3.73 -> 3.80 ms: the kernel is bound by vector issue, and the bands unbalance the XCDs. profiles/r06_ab_k11_xcd_bands.txt)
     for (unsigned item = blockIdx.x * kCompactWaves + wave_in_group; item < n_live; item += gridDim.x * kCompactWaves) {            // wave-uniform
@@ -459,10 +496,16 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
             const float4* __restrict__ pix = a.pixrec + (size_t)tile * kTilePixels * 2;
             const float4* __restrict__ ck = a.ckpt + (size_t)bucket * kTilePixels;
             float4 g[kTilePixels / kWave], cst[kTilePixels / kWave], k[kTilePixels / kWave];
+            [[maybe_unused]] float4 e[kTilePixels / kWave];                       // DEPTH: gD, gA, D_final, T_final
+            [[maybe_unused]] float dk[kTilePixels / kWave];                       // DEPTH: the running depth sum at the checkpoint
 #pragma unroll
             for (int c = 0; c < kTilePixels / kWave; ++c) {                        // all nine loads in flight together
                 const unsigned p = static_cast<unsigned>(c) * kWave + lane;
                 g[c] = pix[2 * p]; cst[c] = pix[2 * p + 1];
+                if constexpr (DEPTH) {
+                    e[c] = x.pixaux[(size_t)tile * kTilePixels + p];
+                    dk[c] = x.ckpt_d != nullptr ? load_float_nt(x.ckpt_d + (size_t)bucket * kTilePixels + p) : 0.0f;   // wave-uniform; without gD the term is 0 anyway
+                }
 #if FGS_CKPT_NT
                 k[c] = load_float4_nt(reinterpret_cast<const float*>(ck + p));
 #else
@@ -483,14 +526,18 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
                     const unsigned slot = n_px + lanes_below(m);
                     const unsigned rel = min(last - first_gaussian, static_cast<unsigned>(kBucket));
                     s_pix[slot] = make_float4(g[c].x, g[c].y, g[c].z, static_cast<float>(rel));
-                    s_xy[slot] = make_float2(x0 + static_cast<float>(p & (kTileW - 1)), y0 + static_cast<float>(p / kTileW));
-                    const float S = (cst[c].x - k[c].x) * g[c].x + (cst[c].y - k[c].y) * g[c].y + (cst[c].z - k[c].z) * g[c].z;   // kb:371-374
+                    if constexpr (DEPTH) reinterpret_cast<float4*>(s_base)[slot] = make_float4(x0 + static_cast<float>(p & (kTileW - 1)), y0 + static_cast<float>(p / kTileW), e[c].x, e[c].y);
+                    else s_xy[slot] = make_float2(x0 + static_cast<float>(p & (kTileW - 1)), y0 + static_cast<float>(p / kTileW));
+                    float S = (cst[c].x - k[c].x) * g[c].x + (cst[c].y - k[c].y) * g[c].y + (cst[c].z - k[c].z) * g[c].z;   // kb:371-374
+                    if constexpr (DEPTH) S += e[c].x * (e[c].z - dk[c]) + e[c].y * (k[c].w - e[c].w);          // gD (D_final - D_ckpt) + gA (T_ckpt - T_final)
                     s_inj[slot] = make_float2(k[c].w, S - g[c].w);
                 }
                 n_px += static_cast<unsigned>(__popcll(m));
             }
             for (unsigned sl = n_px + lane; sl < kRing; sl += kWave) {          // sentinels (rel_last 0: never contributes): 1 to 4 rounds
-                s_pix[sl] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); s_xy[sl] = make_float2(0.0f, 0.0f);
+                s_pix[sl] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if constexpr (DEPTH) reinterpret_cast<float4*>(s_base)[sl] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                else s_xy[sl] = make_float2(0.0f, 0.0f);
             }
 
         }
@@ -502,8 +549,10 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
         float col0 = 0.0f, col1 = 0.0f, col2 = 0.0f, f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
         unsigned footprint = 0;               // candidate tiles of this lane's Gaussian
         uint32_t hot_slot_word = 0;
+        [[maybe_unused]] float z = 0.0f;      // DEPTH: view-space depth of this lane's Gaussian
         if (valid_prim) {
             prim = a.inst_prims[range.x + tp];
+            if constexpr (DEPTH) { const float* m = x.means + 3 * (size_t)prim; z = view_depth(cam, m[0], m[1], m[2]); }
             const float4* r = reinterpret_cast<const float4*>(a.rec + prim);
             const float4 r0 = r[0], r1 = r[1];
             const float4 r2 = r[2];
@@ -544,21 +593,28 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
         float a_h = 0.0f, a_x = 0.0f, a_y = 0.0f;                     // sum hh, sum hh dx, sum hh dy
         float a_xx = 0.0f, a_xy = 0.0f, a_yy = 0.0f;                  // sum hh dx^2, hh dx dy, hh dy^2   (kb:443-448)
         float sT = 0.0f, sS = 0.0f;                                   // the pixel state travelling through the lanes
+        [[maybe_unused]] float a_z = 0.0f;                            // DEPTH: sum w gD = dL/dz
 
         // One pipeline step. `inj` / `px`: what this lane read for THIS step (software pipelined: the reads of the following step
         // are issued first). Contributions are made under the lane mask of `contrib` (EXEC), not by selects: a v_cndmask costs
         // several times an FMA on this chip (tools/valu_rate.hip), and the empty-mask branch of the `if` is the wave-uniform skip.
-        unsigned inj_at = lane0 ? kXyBytes : (kRing - 1u) * 8u;       // byte offsets: lane 0 the slot of the step, other lanes the zero slot
+        unsigned inj_at = lane0 ? kXyBytes : (kRing - 1u) * kXySlot;  // byte offsets: lane 0 the slot of the step, other lanes the zero slot
         const unsigned inj_step = lane0 ? 8u : 0u;
         // byte offset into the 8-byte ring of the slot this lane reads for the step whose reads are issued next: (step - lane) mod 256
         unsigned ring_at = ((0u - lane) & (kRing - 1u)) * 8u;
-        struct PixRead { float4 g; float2 xy; };
+        struct PixRead { float4 g; float2 xy; float gd, ga; };
         auto read_inj = [&]() { const float2 v = *reinterpret_cast<const float2*>(s_base + inj_at); inj_at += inj_step; return v; };
         auto read_pix = [&]() {
             PixRead r;
-            r.xy = *reinterpret_cast<const float2*>(s_base + ring_at);
+            if constexpr (DEPTH) {
+                const float4 v = *reinterpret_cast<const float4*>(s_base + 2u * ring_at);
+                r.xy = make_float2(v.x, v.y); r.gd = v.z; r.ga = v.w;
+            } else {
+                r.xy = *reinterpret_cast<const float2*>(s_base + ring_at);
+                r.gd = 0.0f; r.ga = 0.0f;
+            }
             r.g = *reinterpret_cast<const float4*>(s_base + (2u * ring_at + kPixBase));
-            ring_at = (ring_at + 8u) & (kXyBytes - 1u);
+            ring_at = (ring_at + 8u) & (kRing * 8u - 1u);
             return r;
         };
 #ifdef FGS_PAIR_STATS
@@ -583,7 +639,8 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
                 const float T = sT;
                 const float w = T * alpha;
                 a_c0 += w * px.x; a_c1 += w * px.y; a_c2 += w * px.z;
-                const float cg = col0 * px.x + col1 * px.y + col2 * px.z;
+                float cg = col0 * px.x + col1 * px.y + col2 * px.z;
+                if constexpr (DEPTH) { cg += z * pr.gd + pr.ga; a_z += w * pr.gd; }
                 sS -= w * cg;                                                                    // kb:429 projected on dL/dC
                 const float oma = 1.0f - alpha;
                 const float oma_rcp = fast_rcp(fmaxf(oma, kOneMinusAlphaEps));
@@ -610,7 +667,7 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
         // A Gaussian whose nine sums are all zero has nothing to add (it never passed the alpha test, or only at pixels with a zero
         // image gradient).
         const bool silent = a_h == 0.0f && a_c0 == 0.0f && a_c1 == 0.0f && a_c2 == 0.0f && a_x == 0.0f && a_y == 0.0f
-                            && a_xx == 0.0f && a_xy == 0.0f && a_yy == 0.0f;
+                            && a_xx == 0.0f && a_xy == 0.0f && a_yy == 0.0f && (!DEPTH || a_z == 0.0f);
         if (!(FGS_ABLATE(a) & 1)) {                                                              // kb:459-470
             // The nine sums of a Gaussian leave as its RECORD of nine consecutive floats, SEVEN Gaussians per atomic instruction (lane l of
             // instruction k adds word 63 k + l of the bucket's 64 x 9 block, transposed through the LDS the rings no longer need). Round 4: the
@@ -645,6 +702,10 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
                     const uint32_t rec = s_off[gsn];
                     if (rec != kNoRecord) unsafeAtomicAdd(a.acc + (size_t)rec + comp, s_t[63u * k + lane]);
                 }
+            }
+            if constexpr (DEPTH) {        // dL/dz leaves on its own: one float per lane that has something to add
+                if (valid_prim && a_z != 0.0f)
+                    unsafeAtomicAdd(hot_word != 0u ? x.acc_z_hot + ((size_t)(tile % kHotReplicas) * kMaxHot + (hot_word - 1u)) : x.acc_z + prim, a_z);
             }
         }
 #ifdef FGS_PAIR_STATS
@@ -1292,8 +1353,8 @@ namespace fgs {
 __global__ void __launch_bounds__(256) fold_hot_accumulators_kernel(const BlendBackwardArgs a) {
     const unsigned n_hot = min(*a.hot_count, kMaxHot);
     const unsigned e = blockIdx.x * 256u + threadIdx.x;
-    // this is the last kernel of a backward pass: the accumulator records now hold sums -- a second backward pass over the same buffers (a retained
-    // graph) must clear them itself (stage_pixels_kernel reads the flag)
+    // this is K11's last kernel (K12 reads the records after it): the accumulator records now hold sums -- a second backward pass over the same
+    // buffers (a retained graph) must clear them itself (stage_pixels_kernel reads the flag)
     if (e == 0u) *a.dirty_flag = 1u;
     const unsigned slot = e / kAccRecordWords, k = e % kAccRecordWords;          // consecutive threads: the nine sums of a slot, then the next slot
     if (slot >= n_hot) return;
@@ -1301,6 +1362,25 @@ __global__ void __launch_bounds__(256) fold_hot_accumulators_kernel(const BlendB
 #pragma unroll
     for (unsigned r = 0; r < kHotReplicas; ++r) sum += a.acc_hot[((size_t)r * kMaxHot + slot) * kAccRecordWords + k];
     if (sum != 0.0f) a.acc[(size_t)a.hot_list[slot] * kAccRecordWords + k] += sum;      // one slot per primitive: no other writer at this point
+}
+// the same for dL/dz of a depth backward pass: one thread per hot slot
+__global__ void __launch_bounds__(256) fold_hot_depth_kernel(const BlendBackwardDepthArgs a) {
+    const unsigned n_hot = min(*a.blend.hot_count, kMaxHot);
+    const unsigned slot = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= n_hot) return;
+    float sum = 0.0f;
+#pragma unroll
+    for (unsigned r = 0; r < kHotReplicas; ++r) sum += a.d.acc_z_hot[(size_t)r * kMaxHot + slot];
+    if (sum != 0.0f) a.d.acc_z[a.blend.hot_list[slot]] += sum;                          // one slot per primitive: no other writer at this point
+}
+// after K12 (which has written every element of grad_means): z_i = w2c[2, 0:3] . mean_i + w2c[2, 3], so dL/dmean_i += dL/dz_i w2c[2, 0:3]
+__global__ void __launch_bounds__(256) depth_mean_gradient_kernel(const float* __restrict__ acc_z, const uint32_t* __restrict__ n_touched,
+                                                                  const float* __restrict__ w2c, float* __restrict__ grad_means, const uint32_t n) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || n_touched[i] == 0u) return;
+    const float g = acc_z[i];
+    if (g == 0.0f) return;
+    grad_means[3 * (size_t)i] += g * w2c[8]; grad_means[3 * (size_t)i + 1] += g * w2c[9]; grad_means[3 * (size_t)i + 2] += g * w2c[10];
 }
 #ifdef FGS_DEV_SWITCHES
 __global__ void mark_accumulators_dirty_kernel(uint32_t* flag) { *flag = 1u; }      // the A/B variants that do not end in the fold kernel
@@ -1322,7 +1402,7 @@ hipError_t launch_stage_pixels(const BlendBackwardArgs& a_in, hipStream_t s) {
     BlendBackwardArgs a = a_in;
     if (a.variant >= 3 && a.n_buckets_cap != 0) hipLaunchKernelGGL(plan_blend_backward_kernel, dim3(1), dim3(kTileScanThreads), 0, s, a);
     else a.live_offsets = nullptr;                            // the other variants walk all buckets: no list
-    hipLaunchKernelGGL(stage_pixels_kernel, dim3(a.n_tiles), dim3(kTilePixels), 0, s, a);
+    hipLaunchKernelGGL(stage_pixels_kernel<false>, dim3(a.n_tiles), dim3(kTilePixels), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1360,8 +1440,35 @@ hipError_t launch_blend_backward(const BlendBackwardArgs& a_in, hipStream_t s) {
     // grid-stride over the live list: at most 64 Ki single-wave workgroups, so a scene with few live buckets does not pay
     // for the launch of a quarter of a million empty ones
     const unsigned blocks = a.n_buckets_cap < kBackwardMaxBlocks ? a.n_buckets_cap : kBackwardMaxBlocks;
-    hipLaunchKernelGGL(blend_backward_compact_kernel, dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
+    hipLaunchKernelGGL(blend_backward_compact_kernel<false>, dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
     hipLaunchKernelGGL(fold_hot_accumulators_kernel, dim3(9u * kMaxHot / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The depth forms: always the product formulation (the exhibit variants of the dev library have no depth form)
+hipError_t launch_stage_pixels_depth(const BlendBackwardDepthArgs& a_in, hipStream_t s) {
+    BlendBackwardDepthArgs a = a_in;
+    a.blend.variant = 3;
+    if (a.blend.n_buckets_cap != 0) hipLaunchKernelGGL(plan_blend_backward_kernel, dim3(1), dim3(kTileScanThreads), 0, s, a.blend);
+    else a.blend.live_offsets = nullptr;
+    hipLaunchKernelGGL(stage_pixels_kernel<true>, dim3(a.blend.n_tiles), dim3(kTilePixels), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_backward_depth(const BlendBackwardDepthArgs& a_in, hipStream_t s) {
+    if (a_in.blend.n_buckets_cap == 0) return hipSuccess;
+    BlendBackwardDepthArgs a = a_in;
+    a.blend.variant = 3; a.blend.ablate = 0;
+    const unsigned blocks = a.blend.n_buckets_cap < kBackwardMaxBlocks ? a.blend.n_buckets_cap : kBackwardMaxBlocks;
+    hipLaunchKernelGGL(blend_backward_compact_kernel<true>, dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
+    hipLaunchKernelGGL(fold_hot_accumulators_kernel, dim3(9u * kMaxHot / 256u), dim3(256), 0, s, a.blend);
+    hipLaunchKernelGGL(fold_hot_depth_kernel, dim3(kMaxHot / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_depth_mean_gradient(const float* acc_z, const uint32_t* n_touched, const float* w2c, float* grad_means, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(depth_mean_gradient_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, acc_z, n_touched, w2c, grad_means, n);
     return hipGetLastError();
 }
 

@@ -125,9 +125,12 @@ __device__ unsigned long long g_k10_pair_stats[8];
 // the read-ahead of the next batch alike) and rides to the walk with the colours. Every AUX statement is under `if (AUX)`, and the kernels keep their
 // names: blend_kernel<true> and blend_kernel<false> compile to the instructions they had (the arguments go to the body BY VALUE: by reference the compiler
 // lays the early return out differently), blend_aux_kernel is the third instantiation.
+// TRAINING && AUX (fgs_forward_aux, blend_training_aux_kernel: the fourth instantiation) is the training blend that also returns accumulated opacity
+// and expected depth for a backward pass: next to every (rgb, T) checkpoint it stores the pixel's running depth sum into the plane ckpt_d [B][192]
+// (same condition, same bucket, non-temporal like the checkpoint), which is what K11 needs to start "the depth still to come" at a bucket's first
+// Gaussian. No median here: it is piecewise constant and carries no gradient.
 template <bool TRAINING, bool AUX>
-__device__ __forceinline__ void blend_tile(const BlendArgs a) {
-    static_assert(!(TRAINING && AUX), "the auxiliary maps belong to the inference blend");
+__device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_d = nullptr) {
     const unsigned tile = tile_of_workgroup(blockIdx.x, a.grid_w, a.n_tiles, a.row_group, a.tile_plan, a.grid_h);
     if (tile >= a.n_tiles) return;
 #ifdef FGS_K10_TIMELINE
@@ -196,7 +199,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
             s_a[tid] = r0;
             if (TRAINING) {                                                            // kf:430 (inference clamps at store, ki:200)
                 s_b[tid] = make_float4(r1.x, r1.y, fmaxf(r1.z, 0.0f), fmaxf(r1.w, 0.0f));
-                s_c[tid] = make_float4(fmaxf(r2.x, 0.0f), r2.y, r2.z, 0.0f);
+                s_c[tid] = make_float4(fmaxf(r2.x, 0.0f), r2.y, r2.z, AUX ? r2.w : 0.0f);
             } else {
                 s_b[tid] = r1;
                 s_c[tid] = r2;
@@ -224,6 +227,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
 #else
                 a.ckpt[(size_t)(bucket_base + (batch_start + chunk) / kBucket) * kTilePixels + local] = make_float4(cr, cg, cb, T);
 #endif
+            if (TRAINING && AUX && !done) store_float_nt(ckpt_d + (size_t)(bucket_base + (batch_start + chunk) / kBucket) * kTilePixels + local, depth_sum);
             bool in_l = false, in_r = false;
             const unsigned j = chunk + lane;
             if (j < batch) {                                                           // kf:445-450
@@ -292,7 +296,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
                     if (tested >= gate) {
                         const float w = T * alpha;
                         cr += w * gb.z; cg += w * gb.w; cb += w * blue;
-                        if (AUX) { depth_sum += w * z; depth_med = T > 0.5f ? z : depth_med; }   // T before this Gaussian: a select, no mask merge
+                        if (AUX) { depth_sum += w * z; if (!TRAINING) depth_med = T > 0.5f ? z : depth_med; }   // T before this Gaussian: a select, no mask merge
                         T *= 1.0f - alpha;
                         gate = T < kTransmittanceThreshold ? __builtin_inff() : gate;
                         n_used = batch_start + j0 + k + 1;                             // kf:474
@@ -305,7 +309,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
                         if (tested2 >= gate) {
                             const float w = T * alpha2;
                             cr += w * hb.z; cg += w * hb.w; cb += w * blue2;
-                            if (AUX) { depth_sum += w * z2; depth_med = T > 0.5f ? z2 : depth_med; }
+                            if (AUX) { depth_sum += w * z2; if (!TRAINING) depth_med = T > 0.5f ? z2 : depth_med; }
                             T *= 1.0f - alpha2;
                             gate = T < kTransmittanceThreshold ? __builtin_inff() : gate;
                             n_used = batch_start + j0 + k2 + 1;
@@ -323,7 +327,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
         if (AUX) {                                                                     // image-linear [H,W]; the background is no part of them
             if (a.aux_alpha != nullptr) a.aux_alpha[pix] = 1.0f - T;
             if (a.aux_depth != nullptr) a.aux_depth[pix] = depth_sum;
-            if (a.aux_median != nullptr) a.aux_median[pix] = depth_med;
+            if (!TRAINING && a.aux_median != nullptr) a.aux_median[pix] = depth_med;
         }
         const size_t n_pixels = (size_t)a.width * a.height;
         if (TRAINING) {
@@ -363,6 +367,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a) {
 template <bool TRAINING>
 __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) { blend_tile<TRAINING, false>(a); }
 __global__ void __launch_bounds__(kBlendBlock) blend_aux_kernel(const BlendArgs a) { blend_tile<false, true>(a); }
+__global__ void __launch_bounds__(kBlendBlock) blend_training_aux_kernel(const BlendDepthArgs a) { blend_tile<true, true>(a.blend, a.ckpt_d); }
 
 #ifdef FGS_K10_TIMELINE
 }  // namespace fgs
@@ -496,6 +501,13 @@ hipError_t launch_blend_aux(const BlendArgs& a_in, hipStream_t s) {
     BlendArgs a = a_in;
     if (a.tile_plan == nullptr && (a.row_group == kPlannedBlocks || a.row_group == kBandsThroughPlan)) a.row_group = 0u;
     hipLaunchKernelGGL(blend_aux_kernel, dim3(blend_grid(a)), dim3(kBlendBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_blend_training_aux(const BlendDepthArgs& a_in, hipStream_t s) {
+    BlendDepthArgs a = a_in;
+    if (a.blend.tile_plan == nullptr && (a.blend.row_group == kPlannedBlocks || a.blend.row_group == kBandsThroughPlan)) a.blend.row_group = 0u;
+    hipLaunchKernelGGL(blend_training_aux_kernel, dim3(blend_grid(a.blend)), dim3(kBlendBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -116,23 +116,36 @@ struct InstanceBuffers {              // cf. bu:96-124
 };
 struct BucketBuffers {                // cf. bu:154-163
     uint32_t* tile_index; float4* ckpt; uint2* work_list;
-    static BucketBuffers carve(Carver& c, uint32_t n) {
+    float* ckpt_d;                    // fgs_forward_aux only: the running depth sum beside every checkpoint, [B][192]. At the TAIL: the plain layout is a prefix,
+                                      // so buffers filled by fgs_forward_aux are valid input to every plain backward pass
+    static BucketBuffers carve(Carver& c, uint32_t n, bool with_depth = false) {
         BucketBuffers b;
         b.tile_index = c.take<uint32_t>("tile_index", n);
         b.ckpt = c.take<float4>("ckpt", (size_t)n * kTilePixels);
         b.work_list = c.take<uint2>("work_list", n);        // backward: the live (tile, bucket) pairs
+        b.ckpt_d = with_depth ? c.take<float>("ckpt_d", (size_t)n * kTilePixels) : nullptr;
         return b;
     }
 };
 struct BackwardScratch {
     float* view_dir; float4* pixrec;
-    static BackwardScratch carve(Carver& c, uint32_t n, uint32_t t) {
-        BackwardScratch b;
+    // fgs_backward_aux only (behind the plain layout): staged (gD, gA, D_final, T_final) per pixel, dL/dz per Gaussian and the hot Gaussians' replicas of it
+    float4* pixaux; float* acc_z; float* acc_z_hot;
+    static constexpr size_t kHotDepthFloats = (size_t)kHotReplicas * kMaxHot;
+    static BackwardScratch carve(Carver& c, uint32_t n, uint32_t t, bool with_depth = false) {
+        BackwardScratch b{};
         b.view_dir = c.take<float>("view_dir", (size_t)n * 3);
         b.pixrec = c.take<float4>("pixrec", (size_t)t * kTilePixels * 2);
+        if (with_depth) {
+            b.pixaux = c.take<float4>("pixaux", (size_t)t * kTilePixels);
+            b.acc_z = c.take<float>("acc_z", ((size_t)n + 3) / 4 * 4);
+            b.acc_z_hot = c.take<float>("acc_z_hot", kHotDepthFloats);
+        }
         return b;
     }
 };
+// fgs_forward_state::selector, bit 1: the bucket buffer carries ckpt_d (fgs_forward_aux filled it). Bit 0 is the half of the instance double buffer.
+constexpr int32_t kStateDepthCheckpoints = 2;
 
 // One blob from the caller's allocator: size it for B::carve(args...), ask `resize` for buffer `which`, carve it into `out`.
 template <class B, class... A>
@@ -239,7 +252,8 @@ struct ForwardRequest {
     fgs_resize_fn resize; void* user; fgs_forward_state* state_out; hipStream_t stream;
     float* scores;                        // MODE_SCORES: the output, [N]
     int32_t instance_capacity;            // > 0: the host-synchronisation-free form (fgs_forward_async)
-    // MODE_INFERENCE through fgs_inference_aux: per-pixel maps [H,W] written by the blend beside the image (each may be NULL, not all three)
+    // MODE_INFERENCE through fgs_inference_aux: per-pixel maps [H,W] written by the blend beside the image (each may be NULL, not all three);
+    // MODE_TRAINING through fgs_forward_aux: alpha and expected depth (no median), plus the depth checkpoints a depth backward pass needs
     bool aux = false; float* aux_alpha = nullptr; float* aux_depth = nullptr; float* aux_median = nullptr;
 };
 // What K2..K10 know of the visible list. on_device: the two counts are BOUNDS (primitive count / caller's instance capacity) and the exact
@@ -253,7 +267,11 @@ struct BackwardPlan {
     int32_t n; const fgs_settings* settings; const fgs_forward_state* state;
     Geometry geo; PrimitiveBuffers pb; TileBuffers tb; InstanceBuffers ib; BucketBuffers bb; BackwardScratch sc;
 };
-int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state);
+// with_depth: the scratch blob has the layout of fgs_backward_aux_scratch_bytes. The bucket blob is carved with ckpt_d whenever the state says it has one.
+int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth = false);
 // staging pass + K11. cleared_by_preprocess: a K1 of this library filled the primitive blob and cleared the visible Gaussians' accumulator records
 int run_blend_backward(const BackwardPlan& P, const float* grad_image, const float* image, hipStream_t stream, bool cleared_by_preprocess = true);
+// the same with upstream gradients of accumulated opacity / expected depth (either may be NULL = zero; `depth` = the forward pass's map, read with grad_depth)
+int run_blend_backward_aux(const BackwardPlan& P, const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth,
+                           const float* depth, const float* means, hipStream_t stream);
 }  // namespace fgs

@@ -127,6 +127,11 @@ struct BlendArgs {                      // K10 / inference blend
 hipError_t launch_blend(bool training, const BlendArgs& a, hipStream_t s);
 hipError_t launch_blend_aux(const BlendArgs& a, hipStream_t s);       // the inference blend + accumulated opacity / expected depth / median depth
 hipError_t launch_pruning_scores(const BlendArgs& a, hipStream_t s);   // kernels_pruning_scores.cuh:348-505
+// The training blend that also writes accumulated opacity / expected depth (blend.aux_alpha / aux_depth, either may be nullptr; means and w2c give z)
+// and, beside every checkpoint, the pixel's running depth sum: ckpt_d [B][192]. A struct of its own: BlendArgs, and with it the kernel-argument
+// block of the three other blends, stays what it is.
+struct BlendDepthArgs { BlendArgs blend; float* ckpt_d; };
+hipError_t launch_blend_training_aux(const BlendDepthArgs& a, hipStream_t s);
 
 struct BlendBackwardArgs {              // K11 (+ per-pixel staging pass)
     const uint2* ranges; const uint32_t* bucket_offsets; const uint32_t* inst_prims; const PrimRec* rec;
@@ -150,6 +155,24 @@ struct BlendBackwardArgs {              // K11 (+ per-pixel staging pass)
 };
 hipError_t launch_stage_pixels(const BlendBackwardArgs& a, hipStream_t s);      // per-pixel staging pass
 hipError_t launch_blend_backward(const BlendBackwardArgs& a, hipStream_t s);    // K11 proper
+// K11 with upstream gradients of the accumulated opacity A = 1 - T_final and the expected depth D = sum w z (fgs_backward_aux). Both are two more
+// channels of the blend -- value 1 resp. z per Gaussian, background 0 -- so they fold into the per-pair dot and the remaining-colour scalar; the one
+// new per-Gaussian sum is dL/dz = sum_pixels w gD. The additions travel in a struct of their own: BlendBackwardArgs stays byte for byte what it is.
+struct BlendDepthPart {
+    const float* grad_alpha; const float* grad_depth;   // [H,W] image-linear, each may be nullptr (= zero)
+    const float* depth;                                  // [H,W] the forward pass's expected depth (D_final); read only with grad_depth
+    const float* ckpt_d;                                 // [B][192] running depth sum at every checkpoint (launch_blend_training_aux); read only with grad_depth
+    float4* pixaux;                                      // [T][192] staged (gD, gA, D_final, T_final)
+    const float* means; const float* w2c;                // z of a Gaussian = view_depth(mean): row 2 of w2c
+    float* acc_z;                                        // [N] dL/dz, followed by the hot Gaussians' replicas acc_z_hot [kHotReplicas][kMaxHot]; both cleared by the staging pass
+    float* acc_z_hot;
+    uint32_t clear_z_f4;                                 // 16-byte pieces from acc_z to the end of acc_z_hot
+};
+struct BlendBackwardDepthArgs { BlendBackwardArgs blend; BlendDepthPart d; };
+hipError_t launch_stage_pixels_depth(const BlendBackwardDepthArgs& a, hipStream_t s);
+hipError_t launch_blend_backward_depth(const BlendBackwardDepthArgs& a, hipStream_t s);   // always the product formulation (compact), then both folds
+// after K12: grad_means[i] += acc_z[i] * w2c[2, 0:3] for the Gaussians with n_touched != 0 -- all that z_i's own dependence on mean_i contributes
+hipError_t launch_depth_mean_gradient(const float* acc_z, const uint32_t* n_touched, const float* w2c, float* grad_means, uint32_t n, hipStream_t s);
 
 struct AdamHyper { float step_size, beta1, beta2, eps, bc2_sqrt_rcp; };
 

@@ -197,6 +197,16 @@ struct Projection {
     float a_raw, b, c_raw;
 };
 
+// One float written once and read once a millisecond later (the depth checkpoints of the training blend with maps): non-temporal, like the
+// float4 checkpoints beside them (fgs_wave.h). A compiler without the builtins (a host build of these sources) gets the plain access.
+#if defined(__HIP__) && defined(__clang__)
+__device__ __forceinline__ float load_float_nt(const float* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void store_float_nt(float* p, const float v) { __builtin_nontemporal_store(v, p); }
+#else
+__device__ __forceinline__ float load_float_nt(const float* p) { return *p; }
+__device__ __forceinline__ void store_float_nt(float* p, const float v) { *p = v; }
+#endif
+
 __device__ __forceinline__ float view_depth(const Camera& cam, float mx, float my, float mz) {
 #pragma clang fp contract(off)      // the bits of this value are K1's depth key: the same in a unit built with FMA contraction (blend_forward.hip)
     return cam.r3[0] * mx + cam.r3[1] * my + cam.r3[2] * mz + cam.r3[3];

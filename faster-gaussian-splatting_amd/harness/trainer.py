@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, rasterize, rasterize_aux
+from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_aux, rasterize, rasterize_aux
 
 from .scenes import View
 
@@ -72,6 +72,21 @@ def render_image_training(g: Gaussians, view: View, update_densification_info: b
                           rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color))
 
 
+def render_image_training_aux(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, alpha: bool = True,
+                              depth: bool = True):
+    """render_image_training plus differentiable accumulated opacity and expected depth: (image, alpha or None, depth or None)."""
+    return diff_rasterize_aux(*g.tensors(),
+                              densification_info=g.densification_info if update_densification_info else torch.empty(0),
+                              rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), alpha=alpha, depth=depth)
+
+
+def depth_l1_loss(alpha: torch.Tensor, depth: torch.Tensor, depth_target: torch.Tensor, valid: 'torch.Tensor | None' = None) -> torch.Tensor:
+    """L1 between the mean depth D / A.clamp_min(1e-8) and the target over the valid pixels (default: target > 0)."""
+    valid = depth_target > 0 if valid is None else valid
+    diff = (depth / alpha.clamp_min(1e-8) - depth_target).abs()
+    return (diff * valid).sum() / valid.sum().clamp_min(1)
+
+
 @torch.inference_mode()
 def render_image_benchmark(g: Gaussians, view: View, to_chw: bool = True) -> torch.Tensor:
     """Renderer.py:107-123."""
@@ -111,12 +126,19 @@ def _unit_gradient(loss: torch.Tensor) -> torch.Tensor:
 
 
 def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration: int, *, densification_end: int = 14_900,
-                       loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss) -> torch.Tensor:
+                       loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss, depth_target: 'torch.Tensor | None' = None,
+                       depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
-    optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook)."""
+    optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
+    depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
+    depth supervision through diff_rasterize_aux. Off by default: the step is then exactly the colour-only one."""
     g.update_learning_rate(iteration + 1)
-    image = render_image_training(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
-    loss = loss_fn(image, target)
+    if depth_target is not None and depth_weight > 0.0:
+        image, alpha, depth = render_image_training_aux(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
+        loss = loss_fn(image, target) + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid)
+    else:
+        image = render_image_training(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
+        loss = loss_fn(image, target)
     if loss_scale != 1.0:                 # (two elementwise launches per iteration otherwise)
         loss = loss * loss_scale
     loss.backward(gradient=_unit_gradient(loss))          # = loss.backward() without the fill kernel that seeds it every iteration

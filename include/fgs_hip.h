@@ -61,7 +61,7 @@ typedef struct fgs_forward_state {
     int32_t n_visible;
     int32_t n_instances;
     int32_t n_buckets;   /* capacity of the bucket buffer (upper bound of the device-side count) */
-    int32_t selector;    /* which half of the instance double buffer holds the tile-sorted list */
+    int32_t selector;    /* bit 0: which half of the instance double buffer holds the tile-sorted list; bit 1: fgs_forward_aux left depth checkpoints */
 } fgs_forward_state;
 
 int32_t fgs_abi_version(void);
@@ -103,6 +103,30 @@ int32_t fgs_backward_live(const float* grad_image, const float* image,
                           float* densification_info, void* scratch,
                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream);
 
+/* fgs_forward that also returns, from the same walk, the accumulated opacity alpha = 1 - T_final and the expected depth sum_i w_i z_i (definitions:
+ * fgs_inference_aux below; fp32 [H,W] image-linear, 0 where nothing was blended, the background is no part of them) -- and keeps what a backward pass
+ * needs to differentiate them (the running depth sum beside every checkpoint, at the tail of the bucket buffer: the buffers stay valid input to
+ * fgs_backward / fgs_backward_live / fgs_backward_adam_fused). Either map pointer may be NULL, both NULL is FGS_ERR_INVALID_ARGUMENT. `image` is
+ * fgs_forward's. n_primitives == 0: image = background, maps 0. There is no asynchronous, sharded or record form of it. */
+int32_t fgs_forward_aux(const float* means, const float* scales, const float* rotations, const float* opacities,
+                        const float* sh_coefficients_0, const float* sh_coefficients_rest, int32_t n_primitives,
+                        const fgs_settings* settings, float* image, float* alpha, float* depth_expected,
+                        fgs_resize_fn resize, void* resize_user, fgs_forward_state* state_out, void* stream);
+/* fgs_backward_live with upstream gradients of those two maps: grad_alpha, grad_depth [H,W] (NULL = zero; both NULL is exactly fgs_backward_live and
+ * takes the plain scratch size), depth_expected = the map fgs_forward_aux returned (read with grad_depth only). The expected depth is NOT normalised:
+ * a mean depth depth / alpha is the caller's division, and its chain rule hands both gradients here. A non-NULL grad_depth on buffers that were not
+ * filled by fgs_forward_aux is FGS_ERR_INVALID_ARGUMENT (no depth checkpoints). scratch: fgs_backward_aux_scratch_bytes(). The median depth carries no
+ * gradient; the fused backward + Adam, asynchronous, sharded and record paths take no map gradients. */
+size_t fgs_backward_aux_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height);
+int32_t fgs_backward_aux(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                         const float* means, const float* scales, const float* rotations, const float* opacities,
+                         const float* sh_coefficients_rest,
+                         void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                         float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                         float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                         float* densification_info, void* scratch,
+                         int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream);
+
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
  * the largest count fgs_forward_counts() has reported, scaled with the primitive count -- and every kernel reads the exact counts on the
@@ -132,7 +156,7 @@ int32_t fgs_inference(const float* means, const float* scales, const float* rota
  *   depth_expected = sum_i w_i z_i                (not normalised; divide by alpha for a mean depth; 0 where nothing was blended)
  *   depth_median   = z of the last blended Gaussian whose T_before_i > 0.5: the one that carries T across 0.5 where the pixel becomes more than
  *                    half opaque, otherwise the last one blended; 0 where nothing was blended.
- * `image` is bit-identical to fgs_inference's. The maps carry no gradient. Same buffers, same single host read, everything on `stream`.
+ * `image` is bit-identical to fgs_inference's. These maps carry no gradient (differentiable alpha and expected depth: fgs_forward_aux). Same buffers, same single host read, everything on `stream`.
  * n_primitives == 0: image = background, all maps 0. */
 int32_t fgs_inference_aux(const float* means, const float* scales, const float* rotations, const float* opacities,
                           const float* sh_coefficients_0, const float* sh_coefficients_rest, int32_t n_primitives,
