@@ -391,6 +391,7 @@ int32_t fgs_backward_aux(const float* grad_image, const float* image, const floa
     ShRestArgs sh{};
     fill_backward_args(a, sh, {means, scales, rotations, opacities, nullptr, sh_coefficients_rest}, static_cast<uint32_t>(n_primitives), 1, *settings);
     set_backward_view(a, sh, 0, backward_view(*settings, P.geo, P.pb.n_touched, nullptr, P.pb.acc, P.sc.view_dir));
+    if (grad_depth) a.view[0].acc_z = P.sc.acc_z;
     a.grad_means = grad_means; a.grad_scales = grad_scales; a.grad_rotations = grad_rotations; a.grad_opacities = grad_opacities;
     a.grad_sh0 = grad_sh_coefficients_0; a.densification_info = densification_info;
     if (settings->total_sh_bases_rest > 0 && !grad_sh_coefficients_rest) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL grad_sh_coefficients_rest");

@@ -181,7 +181,7 @@ inline CameraArgs camera_of(const fgs_settings& s, const Geometry& g) {
     return c;
 }
 inline BackwardView backward_view(const fgs_settings& s, const Geometry& g, const uint32_t* n_touched, const uint32_t* slot, const float* acc, float* view_dir) {
-    return BackwardView{camera_of(s, g), n_touched, acc, slot, view_dir};
+    return BackwardView{camera_of(s, g), n_touched, acc, slot, view_dir, nullptr};
 }
 inline int check_settings(const fgs_settings* s) {
     if (!s) return fail(FGS_ERR_INVALID_ARGUMENT, "settings is NULL");

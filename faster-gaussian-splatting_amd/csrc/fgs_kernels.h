@@ -182,6 +182,7 @@ struct BackwardView {                   // what K12 needs per camera view (one o
     const float* acc;                     // single view: records [N][9] (K11's accumulators). Sharded path (several views per launch):
     const uint32_t* slot;                 //   the returned 9-float accumulator RECORDS, that of visible primitive i being record slot[i]
     float* view_dir;                      // [N][3] scratch: unit view direction of visible primitives, consumed by the SH-rest pass
+    const float* acc_z;                   // depth-supervised pass: [N] dL/dz (BlendDepthPart::acc_z), part of K12's "did K11 reach it" test; else nullptr
 };
 struct PreprocessBackwardArgs {         // K12, optionally fused with K13 for the 14 non-SH-rest floats
     const float* means; const float* scales; const float* rotations; const float* opacities; const float* sh_rest;

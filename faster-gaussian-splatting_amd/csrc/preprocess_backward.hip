@@ -43,20 +43,55 @@ template <bool MULTI> __device__ __forceinline__ void sum_into(float& dst, const
 // views of the launch; zeros if no view sees it. st_p: the parameters already in registers (fused mode). KEEP_DIR: the unit view
 // direction and the colour gradient of the (single) view stay in registers for the caller instead of going through the
 // view_dir scratch array.
+// Returns "visible" (some view has the Gaussian on screen: n_touched != 0, kb:45); `reached`: K11 added something to its record in some view.
+// A visible Gaussian that no pixel's walk got to -- hidden behind opaque ones: both blend kernels stop at a tile's last processed
+// Gaussian -- still has the nine zeros K1 cleared its record to, and each of its 59 gradient floats is a product with one of them. Such a
+// view counts in densification_info[0] (the count is of VISIBLE Gaussians; += sqrt(0) on the second statistic is exact and omitted) and is
+// otherwise skipped: no parameter or coefficient load, no projection, neither backward chain; its contribution is +0.0f.
+#ifndef FGS_K12_RECORD_EARLY
+#define FGS_K12_RECORD_EARLY 0   // 1 (A/B): single view, the record is requested together with n_touched -- one dependent step less, 36 B more
+                                 // per invisible Gaussian (measured: profiles/k12_unreached_skip.txt)
+#endif
 template <bool FUSED, bool MULTI, bool KEEP_DIR>
 __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& a, const unsigned i, const float (&st_p)[14],
-                                                  float (&grad)[14], float (&dir)[3], float (&gcol_out)[3]) {
+                                                  float (&grad)[14], float (&dir)[3], float (&gcol_out)[3], bool& reached) {
     const size_t n = a.n;
     float g_mean[3] = {0.0f, 0.0f, 0.0f}, g_scale[3] = {0.0f, 0.0f, 0.0f}, g_rot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     float g_op[1] = {0.0f}, g_sh0[3] = {0.0f, 0.0f, 0.0f};
     bool visible = false;
+    reached = false;
     float m[3] = {0.0f, 0.0f, 0.0f}, s[3] = {0.0f, 0.0f, 0.0f}, q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const int n_views = MULTI ? a.n_views : 1;
     const Camera cam0 = load_camera(a.view[0].cam);     // single view: requested before the visibility test, as are the moments
     for (int vw = 0; vw < n_views; ++vw) {
         const BackwardView& V = a.view[MULTI ? vw : 0];
+        constexpr bool kEarly = !MULTI && FGS_K12_RECORD_EARLY != 0;    // [N][9] records: in bounds for every i (sharded path: slot[] of an invisible one is scratch)
+        float rec[kAccRecordWords];
+        if (kEarly) {
+#pragma unroll
+            for (int k = 0; k < kAccRecordWords; ++k) rec[k] = V.acc[(size_t)i * kAccRecordWords + k];
+        }
         if (V.n_touched[i] == 0) continue;                                             // kb:45
-        if (!visible) {                                                                // parameters: once, whatever the number of views
+        visible = true;
+        // K11's record of this primitive, 9 contiguous floats: single view [N][9]; sharded path: the record that came back, found through the slot table
+        if (!kEarly) {
+            const float* const accp = V.acc + (size_t)(MULTI ? V.slot[i] : i) * kAccRecordWords;
+#pragma unroll
+            for (int k = 0; k < kAccRecordWords; ++k) rec[k] = accp[k];
+        }
+        // reached: any word that is not +-0 (NaN and Inf count and take the full path). Depth-supervised pass: dL/dz of the Gaussian counts too.
+        uint32_t any_bits = 0u;
+#pragma unroll
+        for (int k = 0; k < kAccRecordWords; ++k) any_bits |= __float_as_uint(rec[k]);
+        if (V.acc_z != nullptr) any_bits |= __float_as_uint(V.acc_z[i]);
+        if (a.densification_info != nullptr) a.densification_info[i] += 1.0f;         // kb:194-196
+        const Camera cam = (MULTI && vw > 0) ? load_camera(V.cam) : cam0;
+        if ((any_bits & 0x7fffffffu) == 0u) {
+            // the SH-rest pass of the two-kernel forms multiplies basis(view_dir) by this view's zero colour gradient: give it a finite direction
+            if (!KEEP_DIR && cam.active_sh_bases > 1) { V.view_dir[3 * (size_t)i] = 0.0f; V.view_dir[3 * (size_t)i + 1] = 0.0f; V.view_dir[3 * (size_t)i + 2] = 0.0f; }
+            continue;
+        }
+        if (!reached) {                                                                // parameters: once, whatever the number of views
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 m[k] = FUSED ? st_p[0 + k] : a.means[3 * (size_t)i + k];
@@ -65,10 +100,8 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
 #pragma unroll
             for (int k = 0; k < 4; ++k) q[k] = FUSED ? st_p[10 + k] : a.rotations[4 * (size_t)i + k];
         }
-        visible = true;
-        const Camera cam = (MULTI && vw > 0) ? load_camera(V.cam) : cam0;
-        // K11's record of this primitive, 9 contiguous floats: single view [N][9]; sharded path: the record that came back, found through the slot table
-        const float* const accp = V.acc + (size_t)(MULTI ? V.slot[i] : i) * kAccRecordWords;
+        reached = true;
+        const float* const accp = rec;
         constexpr size_t es = 1;
         const float gcol[3] = {accp[6 * es], accp[7 * es], accp[8 * es]};
         if (KEEP_DIR) { gcol_out[0] = gcol[0]; gcol_out[1] = gcol[1]; gcol_out[2] = gcol[2]; }
@@ -160,8 +193,7 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
         const float dj13 = cam.r3[0] * djw1[0] + cam.r3[1] * djw1[1] + cam.r3[2] * djw1[2];
         const float dj23 = cam.r3[0] * djw2[0] + cam.r3[1] * djw2[1] + cam.r3[2] * djw2[2];
         const float gm2x = accp[0], gm2y = accp[es];
-        if (a.densification_info != nullptr) {                                         // kb:194-201
-            a.densification_info[i] += 1.0f;
+        if (a.densification_info != nullptr) {                                         // kb:197-201 (the count of visible views: above)
             const float nx = 0.5f * (gm2x * cam.width), ny = 0.5f * (gm2y * cam.height);
             a.densification_info[n + i] += sqrtf(nx * nx + ny * ny);
         }
@@ -221,7 +253,8 @@ __global__ void __launch_bounds__(kPreprocessBackwardBlock) preprocess_backward_
             }
     }
     float grad[14], dir[3], gcol[3];
-    const bool visible = gaussian_backward<FUSED, MULTI, false>(a, i, st_p, grad, dir, gcol);
+    bool reached;
+    gaussian_backward<FUSED, MULTI, false>(a, i, st_p, grad, dir, gcol, reached);
 
     // Every element is written (zeros if invisible).
     float* const outs[5] = {a.grad_means, a.grad_sh0, a.grad_opacities, a.grad_scales, a.grad_rotations};
@@ -233,7 +266,7 @@ __global__ void __launch_bounds__(kPreprocessBackwardBlock) preprocess_backward_
             const int o = kGroupOffset[grp] + k;
             if (!FUSED) {
                 if (!MULTI || !a.accumulate) outs[grp][e] = grad[o];       // view batches after the first add (sharded path only)
-                else if (visible) outs[grp][e] += grad[o];
+                else if (reached) outs[grp][e] += grad[o];
             } else {
                 adam_update(st_p[o], st_m[o], st_v[o], grad[o], a.h[grp]);
                 a.p[grp][e] = st_p[o]; a.m[grp][e] = st_m[o]; a.v[grp][e] = st_v[o];
@@ -251,14 +284,14 @@ __global__ void __launch_bounds__(kPreprocessBackwardBlock) preprocess_backward_
 constexpr uint32_t kShFactorStride = 18;                 // floats per Gaussian: colour gradient 3, basis values 15
 constexpr uint32_t kShFactorFloats = kWave * kShFactorStride;
 
-__device__ __forceinline__ void put_sh_factors(float* const slice, const uint32_t lane, const bool visible, const float (&dir)[3],
+__device__ __forceinline__ void put_sh_factors(float* const slice, const uint32_t lane, const bool reached, const float (&dir)[3],
                                                const float (&gcol)[3], const int active_sh_bases) {
     float B[15];
 #pragma unroll
     for (int k = 0; k < 15; ++k) B[k] = 0.0f;                         // degrees above the active one keep a zero gradient
-    if (visible && active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], active_sh_bases, B);
+    if (reached && active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], active_sh_bases, B);
     float* const mine = slice + lane * kShFactorStride;
-    mine[0] = gcol[0]; mine[1] = gcol[1]; mine[2] = gcol[2];           // zeros for an invisible Gaussian
+    mine[0] = gcol[0]; mine[1] = gcol[1]; mine[2] = gcol[2];           // zeros for an invisible or unreached Gaussian
 #pragma unroll
     for (int k = 0; k < 15; ++k) mine[3 + k] = B[k];
 }
@@ -350,10 +383,10 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
             for (int k = 0; k < kGroupWidth[grp]; ++k) st_p[kGroupOffset[grp] + k] = a.p[grp][(size_t)ic * kGroupWidth[grp] + k];
     }
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
-    bool visible = false;
+    bool reached = false;
 #pragma unroll
     for (int k = 0; k < 14; ++k) grad[k] = 0.0f;
-    if (in_range) visible = gaussian_backward<true, false, true>(a, i, st_p, grad, dir, gcol);
+    if (in_range) gaussian_backward<true, false, true>(a, i, st_p, grad, dir, gcol, reached);
     if (whole) {
         float4 in[2][5];
 #pragma unroll
@@ -421,10 +454,10 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
     }
     if (R == 0) return;
 
-    // ---- the wave's SH-rest gradient factors -> LDS (skipped when no lane of the wave is visible: the block is zero) ----
-    const bool any_visible = wave_ballot(visible) != 0;
-    if (any_visible) {
-        put_sh_factors(slice, lane, visible, dir, gcol, sh.active_sh_bases);
+    // ---- the wave's SH-rest gradient factors -> LDS (skipped when K11 reached no Gaussian of the wave: the block is zero) ----
+    const bool any_reached = wave_ballot(reached) != 0;
+    if (any_reached) {
+        put_sh_factors(slice, lane, reached, dir, gcol, sh.active_sh_bases);
         wave_lds_fence();
     }
 
@@ -445,14 +478,14 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
         for (int u = 0; u < kFusedUnroll; ++u) {
             const uint32_t e = e0 + 4u * kWave * static_cast<uint32_t>(u);
             if (full[u]) {
-                const float4 g = any_visible ? sh_rest_gradient_piece<RT>(slice, e, R) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                const float4 g = any_reached ? sh_rest_gradient_piece<RT>(slice, e, R) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 adam_update(p4[u].x, m4[u].x, v4[u].x, g.x, sh.h); adam_update(p4[u].y, m4[u].y, v4[u].y, g.y, sh.h);
                 adam_update(p4[u].z, m4[u].z, v4[u].z, g.z, sh.h); adam_update(p4[u].w, m4[u].w, v4[u].w, g.w, sh.h);
                 store_float4_nt(P + e, p4[u]); store_float4_nt(M + e, m4[u]); store_float4_nt(V + e, v4[u]);
             } else if (e < count) {                                                    // ragged tail of the last wave (< 4 floats), or unaligned tensors
                 for (uint32_t j = e; j < count && j < e + 4u; ++j) {
                     float pp = P[j], mm = M[j], vv = V[j];
-                    adam_update(pp, mm, vv, any_visible ? sh_rest_gradient_at<RT>(slice, j, R) : 0.0f, sh.h);
+                    adam_update(pp, mm, vv, any_reached ? sh_rest_gradient_at<RT>(slice, j, R) : 0.0f, sh.h);
                     P[j] = pp; M[j] = mm; V[j] = vv;
                 }
             }
@@ -479,9 +512,9 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
     const bool in_range = i < a.n;
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
     const float unused[14] = {};
-    bool visible = false;
+    bool visible = false, reached = false;
     if (in_range) {
-        visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol);
+        visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol, reached);
         // scalar stores at a stride of 4 w bytes: the write path combines them. Staging the wave's 64 x w block in LDS and storing it as one
         // coalesced 16-byte access per lane -- what pays in the fused kernel, where the same floats are also LOADED three times -- measured
         // 0.261 vs 0.252 ms here (profiles/archive/r02_ab_k12_coalesced_stores.txt)
@@ -498,14 +531,14 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
             }
     }
     float* const slice = s_grad[wv];
-    const bool any_visible = wave_ballot(visible) != 0;
-    if (a.live_blocks != nullptr && lane == 0) a.live_blocks[first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64
+    const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
+    if (a.live_blocks != nullptr && lane == 0) a.live_blocks[first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
     if (R == 0) return;
-    if (any_visible) {
+    if (any_reached) {                                                 // a wave K11 reached no Gaussian of writes its SH-rest block as zeros
         float B[15];
 #pragma unroll
         for (int k = 0; k < 15; ++k) B[k] = 0.0f;
-        if (visible && sh.active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], sh.active_sh_bases, B);
+        if (reached && sh.active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], sh.active_sh_bases, B);
         float* const mine = slice + lane * R * 3u;
 #pragma unroll
         for (int k = 0; k < 15; ++k)
@@ -516,14 +549,14 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
     float* const out = sh.grad_sh_rest + (size_t)first * R * 3u;
     for (uint32_t e = 4u * lane; e < count; e += 4u * kWave) {
         if (e + 4u <= count && a.vector_ok) {                          // 16-byte stores need a 16-byte aligned gradient tensor (checked at launch)
-            const float4 g = any_visible ? *reinterpret_cast<const float4*>(slice + e) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const float4 g = any_reached ? *reinterpret_cast<const float4*>(slice + e) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #if FGS_K12_NT_STORES
             store_float4_nt(out + e, g);
 #else
             *reinterpret_cast<float4*>(out + e) = g;
 #endif
         } else {
-            for (uint32_t j = e; j < count && j < e + 4u; ++j) out[j] = any_visible ? slice[j] : 0.0f;
+            for (uint32_t j = e; j < count && j < e + 4u; ++j) out[j] = any_reached ? slice[j] : 0.0f;
         }
     }
 }
