@@ -222,10 +222,12 @@ class Backend:
         return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
 
     def backward(self, densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings,
-                 state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None) -> tuple:
+                 state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
+                 reached_blocks: Optional[torch.Tensor] = None) -> tuple:
         """`out`: optional six preallocated gradient tensors (e.g. views into one contiguous arena for a single RCCL call).
-        `live_blocks`: optional uint8 [ceil(N / 64)] on the device, filled with 1 / 0 per block of 64 Gaussians: 0 = every gradient of the block
-        is zero (still written) -- what adam_step_multi(live_blocks=...) needs to skip reading those zeros."""
+        `live_blocks`, `reached_blocks`: optional uint8 [ceil(N / 64)] on the device, filled with 1 / 0 per block of 64 Gaussians: some Gaussian of the
+        block is visible / was reached by the backward blend pass. 0 = every gradient of the block is zero (still written) -- what
+        adam_step_multi(live_blocks=...) needs to skip reading those zeros; `reached_blocks` flags a superset of the zero blocks."""
         device = self._check_params((means, scales, rotations, opacities, sh_rest), ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest'))
         keep: list = []
         n = means.shape[0]
@@ -245,22 +247,25 @@ class Backend:
             raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
         scratch = self._scratch(n, settings, device)
         st = _lib.ForwardState(*state)
-        if live_blocks is not None and (live_blocks.dtype != torch.uint8 or live_blocks.device != device or not live_blocks.is_contiguous()
-                                        or live_blocks.numel() != (n + 63) // 64):
-            raise RuntimeError('live_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
-        self._check(self.lib.fgs_backward_live(_ptr(grad_image), _ptr(image), _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities),
-                                               _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]),
-                                               _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
-                                               _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _stream_of(device)),
+        for name, flags in (('live_blocks', live_blocks), ('reached_blocks', reached_blocks)):
+            if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
+                raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
+        self._check(self.lib.fgs_backward_reached(_ptr(grad_image), _ptr(image), None, None, None, _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities),
+                                                  _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]),
+                                                  _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
+                                                  _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+                                                  _stream_of(device)),
                     'fgs_backward')
         return grads
 
     def backward_aux(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
-                     buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None) -> tuple:
+                     buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
+                     reached_blocks: Optional[torch.Tensor] = None) -> tuple:
         """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero; both None is `backward`
         exactly). `depth` is the expected-depth map the forward pass returned (needed with grad_depth)."""
         if grad_alpha is None and grad_depth is None:
-            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state, out, live_blocks)
+            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state, out, live_blocks,
+                                 reached_blocks)
         device = self._check_params((means, scales, rotations, opacities, sh_rest), ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest'))
         keep: list = []
         n = means.shape[0]
@@ -287,15 +292,16 @@ class Backend:
         dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
         if dens is not None and (dens.dtype != torch.float32 or not dens.is_contiguous() or dens.device != device or dens.numel() != 2 * n):
             raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
-        if live_blocks is not None and (live_blocks.dtype != torch.uint8 or live_blocks.device != device or not live_blocks.is_contiguous()
-                                        or live_blocks.numel() != (n + 63) // 64):
-            raise RuntimeError('live_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
+        for name, flags in (('live_blocks', live_blocks), ('reached_blocks', reached_blocks)):
+            if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
+                raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
         scratch = self._scratch_aux(n, settings, device)
         st = _lib.ForwardState(*state)
-        self._check(self.lib.fgs_backward_aux(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
-                                              _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
-                                              _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
-                                              _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _stream_of(device)),
+        self._check(self.lib.fgs_backward_reached(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
+                                                  _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
+                                                  _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
+                                                  _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+                                                  _stream_of(device)),
                     'fgs_backward_aux')
         return grads
 

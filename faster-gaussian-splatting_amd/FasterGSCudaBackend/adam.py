@@ -72,8 +72,9 @@ class FusedAdam(torch.optim.Adam):
         for (beta1, beta2, eps, _device), updates in launches.items():
             for first in range(0, len(updates), _GROUPS_PER_LAUNCH):
                 chunk = updates[first:first + _GROUPS_PER_LAUNCH]
-                # gradients that are still exactly what the rasterizer's backward pass wrote come with its per-block "any visible" flags: the
-                # zeros of dead blocks are not read back (rasterization.match_live_blocks; bit-identical result, ~4 % less optimizer traffic)
+                # gradients that are still exactly what the rasterizer's backward pass wrote come with its per-block "any reached" flags: the
+                # zeros of blocks it reached no Gaussian of are not read back (rasterization.match_live_blocks; bit-identical result; gradient
+                # reads fall to the reached blocks' share: ~0.04 of them in a dense opaque scene, 0.4-0.5 in a translucent one)
                 live = match_live_blocks([u.grad for u in chunk], owned) if len(updates) <= _GROUPS_PER_LAUNCH else None
                 backend.adam_step_multi([u.grad for u in chunk], [u.param for u in chunk], [u.exp_avg for u in chunk],
                                         [u.exp_avg_sq for u in chunk], [u.step for u in chunk], [u.lr for u in chunk], beta1, beta2, eps,

@@ -73,16 +73,19 @@ class async_forward_scope:
             _ASYNC_SCOPES.pop(name, None)
 
 # ---- live-block hand-over from this backward pass to FusedAdam.step ------------------------------------------------------------------
-# One third of the Gaussians is invisible in a view; their gradients are zeros that the backward pass writes (the gradient tensors are dense and
-# valid for any reader) and the optimizer reads back. The backward pass also leaves one byte per block of 64 Gaussians ("any visible"), and
-# FusedAdam.step skips READING the gradients of dead blocks -- if, and only if, the gradients it is handed are still exactly what this
-# backward pass wrote. That is established without trusting anybody: the six gradients are views into ONE arena that this registry keeps alive
-# (their addresses cannot be re-used by another tensor while registered). The registry holds the ARENA and the views' addresses / shapes, never
+# Most gradient rows of a pass are zeros that the backward pass writes (the gradient tensors are dense and valid for any reader) and the optimizer
+# reads back: one third of the Gaussians is invisible in a view, and of the visible ones the backward blend pass reaches only those that are not
+# hidden behind opaque ones (1 % of them in a dense opaque scene, 40-50 % in a translucent one). The backward pass leaves two bytes per block of
+# 64 Gaussians, "any visible" and "any reached" (fgs_backward_reached), and this registry hands the REACHED array to FusedAdam.step, which skips
+# READING the gradients of blocks flagged 0 -- 0.96 of all blocks in the dense scene, 0.5-0.6 in the translucent one -- if, and only if, the
+# gradients it is handed are still exactly what this backward pass wrote. That is established without trusting anybody: the six gradients are views
+# into ONE arena that this registry keeps alive (their addresses cannot be re-used by another tensor while registered).
+# The registry holds the ARENA and the views' addresses / shapes, never
 # the view tensors themselves: autograd adopts an incoming gradient as `.grad` only if nobody else references that tensor (it looks at the
 # reference count of the view, not of its storage) and clones it otherwise -- 708 MB per iteration at 3 M Gaussians. A match needs the same address, the same shape and an unchanged version counter (views share the arena's: any
 # in-place edit -- accumulation of a second backward, clipping, scaling -- shows). Anything else takes the ordinary path; results are
 # bit-identical either way. Writes the version counter does not see (`.grad.data.add_(...)`, raw pointers) are the kernel's business: it reads
-# one sentinel float per dead block and tensor and, unless that is +-0, the block's gradients after all (csrc/preprocess_backward.hip).
+# one sentinel float per flagged-0 block and tensor and, unless that is +-0, the block's gradients after all (csrc/preprocess_backward.hip).
 # The registry holds ONE registration per model, keyed by the address of the `means` tensor of the pass (two models in one process do not evict
 # each other's registration; a model's next backward pass replaces its own). An optimizer names the parameters it owns when it asks.
 _LIVE = {'enabled': True, 'slots': {}, 'matched': 0, 'missed': 0}
@@ -322,9 +325,9 @@ class _Rasterize(torch.autograd.Function):
         if _LIVE['enabled'] and _GRAD_OUT is None and n > 0:
             total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
             arena, views = _gradient_arena(((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3)), means.device)
-            flags = torch.empty((n + 63) // 64, dtype=torch.uint8, device=means.device)
+            live, flags = torch.empty((2, (n + 63) // 64), dtype=torch.uint8, device=means.device)      # "any visible" / "any reached": the optimizer gets the latter
             grads = default_backend().backward(ctx.densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest,
-                                               buffers, ctx.rasterizer_settings, state, out=views, live_blocks=flags)
+                                               buffers, ctx.rasterizer_settings, state, out=views, live_blocks=live, reached_blocks=flags)
             slots = _LIVE['slots']
             slots.pop(means.data_ptr(), None)
             slots[means.data_ptr()] = {'arena': arena, 'version': arena._version, 'flags': flags,

@@ -364,7 +364,6 @@ int32_t fgs_backward_live(const float* grad_image, const float* image,
                             grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks, stream_);
 }
 
-// K11 and K12 of the single-GPU path. Without map gradients this IS fgs_backward_live: the plain staging pass and K11, the plain scratch layout.
 int32_t fgs_backward_aux(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
                          const float* means, const float* scales, const float* rotations, const float* opacities,
                          const float* sh_coefficients_rest,
@@ -373,6 +372,24 @@ int32_t fgs_backward_aux(const float* grad_image, const float* image, const floa
                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
                          float* densification_info, void* scratch,
                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream_) {
+    return fgs_backward_reached(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                                primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                                grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                                nullptr, stream_);
+}
+
+// K11 and K12 of the single-GPU path. Without map gradients this IS fgs_backward_live: the plain staging pass and K11, the plain scratch layout.
+// reached_blocks: K12's second flag per block of 64 ("K11 reached a Gaussian of it"); with a depth gradient the per-lane test includes dL/dz (acc_z), so a
+// block flagged 0 stays zero through launch_depth_mean_gradient as well.
+int32_t fgs_backward_reached(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                             const float* means, const float* scales, const float* rotations, const float* opacities,
+                             const float* sh_coefficients_rest,
+                             void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                             float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                             float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                             float* densification_info, void* scratch,
+                             int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                             uint8_t* reached_blocks, void* stream_) {
     const bool with_maps = grad_alpha != nullptr || grad_depth != nullptr;
     BackwardPlan P;
     if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state, with_maps)) return rc;
@@ -399,9 +416,11 @@ int32_t fgs_backward_aux(const float* grad_image, const float* image, const floa
     if (g_fused_single_kernel) {           // K12 (bwd:94) as one kernel
         StageScope t(ST_PREPROCESS_BACKWARD, stream);
         a.live_blocks = live_blocks;
+        a.reached_blocks = reached_blocks;
         FGS_HIP(launch_backward_gradients(a, sh, stream));
     } else {
         if (live_blocks != nullptr) FGS_HIP(hipMemsetAsync(live_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // A/B form: no flags, every block "live"
+        if (reached_blocks != nullptr) FGS_HIP(hipMemsetAsync(reached_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // ... and "reached"
         { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_preprocess_backward(false, a, stream)); }   // round-1 form: geometry kernel + SH-rest kernel
         if (settings->total_sh_bases_rest > 0) { StageScope t(ST_SH_REST_BACKWARD, stream); FGS_HIP(launch_sh_rest_backward(false, sh, stream)); }
     }

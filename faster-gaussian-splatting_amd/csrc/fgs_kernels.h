@@ -196,6 +196,9 @@ struct PreprocessBackwardArgs {         // K12, optionally fused with K13 for th
     // single-kernel unfused form only: [ceil(n / 64)] bytes or nullptr -- 1 if any Gaussian of the block 64 b .. 64 b + 63 is visible, 0 if the
     // block's gradients are all zero (they are still written); lets the optimizer skip the read of those zeros (launch_adam)
     uint8_t* live_blocks;
+    // same form, same size, or nullptr -- 1 if K11 REACHED some Gaussian of the block (gaussian_backward's test, dL/dz of a depth-supervised pass included),
+    // 0 if every row of the block is +-0 in all six gradient tensors: invisible blocks and the visible ones hidden behind opaque Gaussians
+    uint8_t* reached_blocks;
     int vector_ok;                        // set by the launchers: every per-Gaussian tensor of the call is 16-byte aligned (coalesced 16-byte phase A)
 };
 hipError_t launch_preprocess_backward(bool fused_adam, const PreprocessBackwardArgs& a, hipStream_t s);

@@ -533,6 +533,7 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
     float* const slice = s_grad[wv];
     const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
     if (a.live_blocks != nullptr && lane == 0) a.live_blocks[first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
+    if (a.reached_blocks != nullptr && lane == 0) a.reached_blocks[first >> 6] = any_reached ? 1 : 0;   // 0: all 59 floats of every row of the block were written as +0
     if (R == 0) return;
     if (any_reached) {                                                 // a wave K11 reached no Gaussian of writes its SH-rest block as zeros
         float B[15];
@@ -823,6 +824,23 @@ template <bool NT> __device__ __forceinline__ void store4(float* p, const float4
     else *reinterpret_cast<float4*>(p) = v;
 }
 
+// Does the optimizer have to READ the gradient elements first .. last (at most four consecutive floats of the [N, L] tensor)? They cover the rows
+// first / L .. last / L, which lie in at most two consecutive blocks of 64 Gaussians. Both flagged 0: every element is a zero the backward pass wrote --
+// skip the read (the kernel is HBM-bound; the index arithmetic is free).
+__device__ __forceinline__ bool adam_gradient_needed(const AdamArgs& a, const AdamGroup& G, const int64_t first, const int64_t last) {
+    if (a.live_blocks == nullptr || G.row_len == 0u) return true;
+    const uint32_t r0 = static_cast<uint32_t>(first) / G.row_len, r1 = static_cast<uint32_t>(last) / G.row_len;
+    const uint32_t b0 = r0 >> 6, b1 = r1 >> 6;
+    if ((a.live_blocks[b0] | a.live_blocks[b1]) != 0) return true;
+    // Belt and braces: the promise rests on the caller's proof that nobody touched the gradients since the backward pass,
+    // and a write that bypasses the framework's bookkeeping (`.grad.data.add_(...)`, a raw-pointer kernel) cannot be seen by
+    // it. One SENTINEL float per flagged-0 block and tensor (the first element of the block: the same cached 4 bytes for every
+    // float4 of the block) is read anyway; anything but +-0 there -- a whole-tensor edit such as hand-written weight decay,
+    // NaN / Inf -- and the block's gradients are read after all.
+    const float s0 = G.grad[(size_t)b0 * 64u * G.row_len], s1 = G.grad[(size_t)b1 * 64u * G.row_len];
+    return !(s0 == 0.0f) || !(s1 == 0.0f);
+}
+
 template <int U, bool NT>
 __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
     // a.reverse: workgroups walk the arenas from the end -- the gradient elements the backward pass wrote LAST are the ones most likely to
@@ -840,25 +858,7 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
         const int64_t base = block_base + ((int64_t)u * 256 + threadIdx.x) * 4;
         full[u] = base + 4 <= G.n;
         if (full[u]) {
-            // the float4 covers the rows base / L .. (base + 3) / L of the [N, L] gradient; they lie in at most two consecutive blocks of 64
-            // Gaussians. Both dead: every element is a zero the backward pass wrote -- skip the read (the kernel is HBM-bound; the index
-            // arithmetic is free)
-            bool need = true;
-            if (a.live_blocks != nullptr && G.row_len != 0u) {
-                const uint32_t r0 = static_cast<uint32_t>(base) / G.row_len, r1 = static_cast<uint32_t>(base + 3) / G.row_len;
-                const uint32_t b0 = r0 >> 6, b1 = r1 >> 6;
-                need = (a.live_blocks[b0] | a.live_blocks[b1]) != 0;
-                if (!need) {
-                    // Belt and braces: the promise rests on the caller's proof that nobody touched the gradients since the backward pass,
-                    // and a write that bypasses the framework's bookkeeping (`.grad.data.add_(...)`, a raw-pointer kernel) cannot be seen by
-                    // it. One SENTINEL float per dead block and tensor (the first element of the block: the same cached 4 bytes for every
-                    // float4 of the block) is read anyway; anything but +-0 there -- a whole-tensor edit such as hand-written weight decay,
-                    // NaN / Inf -- and the block's gradients are read after all.
-                    const float s0 = G.grad[(size_t)b0 * 64u * G.row_len], s1 = G.grad[(size_t)b1 * 64u * G.row_len];
-                    need = !(s0 == 0.0f) || !(s1 == 0.0f);
-                }
-            }
-            g4[u] = need ? load4<NT>(G.grad + base) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            g4[u] = adam_gradient_needed(a, G, base, base + 3) ? load4<NT>(G.grad + base) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             p4[u] = load4<NT>(G.param + base);
             m4[u] = load4<NT>(G.exp_avg + base);
             v4[u] = load4<NT>(G.exp_avg_sq + base);
@@ -874,9 +874,11 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
             store4<NT>(G.exp_avg + base, m4[u]);
             store4<NT>(G.exp_avg_sq + base, v4[u]);
         } else {
+            // the tensor's last (fewer than four) floats: the same promise, or a tensor of 4 k + 1 .. 3 floats would have its tail read whatever the flags say
+            const bool need = base < G.n && adam_gradient_needed(a, G, base, G.n - 1);
             for (int64_t e = base; e < G.n && e < base + 4; ++e) {
                 float pp = G.param[e], mm = G.exp_avg[e], vv = G.exp_avg_sq[e];
-                adam_update(pp, mm, vv, G.grad[e], G.h);
+                adam_update(pp, mm, vv, need ? G.grad[e] : 0.0f, G.h);
                 G.param[e] = pp; G.exp_avg[e] = mm; G.exp_avg_sq[e] = vv;
             }
         }

@@ -126,6 +126,23 @@ int32_t fgs_backward_aux(const float* grad_image, const float* image, const floa
                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
                          float* densification_info, void* scratch,
                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks, void* stream);
+/* fgs_backward_aux plus a second byte per block of 64 consecutive Gaussians: reached_blocks[b] = 1 if the backward blend pass REACHED some Gaussian
+ * 64 b .. 64 b + 63 -- added anything that is not +-0 to its nine per-Gaussian sums or, with grad_depth, to its dL/dz; a Gaussian of more than 256 tiles
+ * counts through its folded record. 0 is a PROMISE: every row of the block is +-0 in all six gradient tensors (written all the same), also after the
+ * depth term has been added to grad_means -- the per-Gaussian test that feeds the flag includes dL/dz, so the flag is exact on the map-gradient path
+ * too, not a copy of live_blocks. That covers the invisible blocks and the visible ones hidden behind opaque Gaussians (two thirds of all blocks of a
+ * dense scene). reached_blocks[b] <= live_blocks[b]; live_blocks keeps its meaning ("any visible"). [ceil(n_primitives / 64)] bytes each, either may be
+ * NULL (both NULL, no map gradients = fgs_backward); the last block may be partial; n_primitives == 0 writes nothing. Either array is a valid
+ * `live_blocks` argument of fgs_adam_step_multi_live for exactly these gradient tensors; reached_blocks spares it more reads. */
+int32_t fgs_backward_reached(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                             const float* means, const float* scales, const float* rotations, const float* opacities,
+                             const float* sh_coefficients_rest,
+                             void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                             float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                             float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                             float* densification_info, void* scratch,
+                             int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                             uint8_t* reached_blocks, void* stream);
 
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
@@ -178,8 +195,8 @@ int32_t fgs_adam_step(const float* grad, float* param, float* exp_avg, float* ex
 int32_t fgs_adam_step_multi(int32_t n_groups, const float* const* grads, float* const* params, float* const* exp_avgs,
                             float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
                             double beta1, double beta2, double eps, void* stream);
-/* The same with the caller's PROMISE that gradient rows of dead blocks are zero: live_blocks as written by fgs_backward_live for exactly these
- * gradient tensors (device, [ceil(N / 64)] bytes), floats_per_gaussian[k] = row length of group k ([host]). Gradients of dead blocks are not
+/* The same with the caller's PROMISE that gradient rows of dead blocks are zero: live_blocks as written by fgs_backward_live (or, sparing more reads,
+ * reached_blocks as written by fgs_backward_reached) for exactly these gradient tensors (device, [ceil(N / 64)] bytes), floats_per_gaussian[k] = row length of group k ([host]). Gradients of dead blocks are not
  * read -- except one sentinel float per dead block and tensor (the block's first element): if it is not +-0 the block is read after all, so a
  * whole-tensor edit behind the caller's back does not go unnoticed; parameters and moments of every Gaussian are updated as always (the result
  * is bit-identical to fgs_adam_step_multi). NULL = no promise. */
