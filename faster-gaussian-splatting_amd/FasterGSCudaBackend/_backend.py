@@ -338,26 +338,49 @@ class Backend:
                                            float(lr), float(beta1), float(beta2), float(eps), _stream_of(device)), 'fgs_adam_step')
 
     def adam_step_multi(self, grads, params, exp_avgs, exp_avg_sqs, steps, lrs, beta1: float, beta2: float, eps: float,
-                        live_blocks: Optional[torch.Tensor] = None) -> None:
+                        live_blocks: Optional[torch.Tensor] = None, quiet_blocks: Optional[torch.Tensor] = None) -> None:
         """`live_blocks` (as filled by backward(live_blocks=...) for EXACTLY these gradient tensors, all of them [N, ...]): a promise that the
-        gradient rows of blocks flagged 0 are zero; they are not read. The result is bit-identical either way."""
+        gradient rows of blocks flagged 0 are zero; they are not read. The result is bit-identical either way.
+        `quiet_blocks` (uint8 [ceil(N / 64)], the caller's own; fgs_adam_step_multi_quiet): 1 = a promise that both moments of the block are zero in
+        every group. Blocks that are quiet and not live are neither read nor written (the identity); the call clears the flag of every block it
+        reads a gradient for, and ALL flags if it cannot use them (no live_blocks, eps <= 0, a step size that is not finite)."""
         k = len(params)
         if k == 0:
             return
         device = self._check_params(tuple(grads) + tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['adam tensor'] * (4 * k))
         arr = lambda ts: (C.c_void_p * k)(*[_ptr(t) for t in ts])
         rows = None
-        if live_blocks is not None:
+        if live_blocks is not None or quiet_blocks is not None:
             n = params[0].shape[0]
             if any(p.dim() < 1 or p.shape[0] != n for p in params) or n == 0:
-                raise RuntimeError('live_blocks needs parameter tensors that all have one row per Gaussian')
-            if live_blocks.dtype != torch.uint8 or live_blocks.device != device or not live_blocks.is_contiguous() or live_blocks.numel() != (n + 63) // 64:
-                raise RuntimeError('live_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
+                raise RuntimeError('live_blocks / quiet_blocks need parameter tensors that all have one row per Gaussian')
+            for name, flags in (('live_blocks', live_blocks), ('quiet_blocks', quiet_blocks)):
+                if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
+                    raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
             rows = (C.c_int32 * k)(*[p.numel() // n for p in params])
-        self._check(self.lib.fgs_adam_step_multi_live(k, arr(grads), arr(params), arr(exp_avgs), arr(exp_avg_sqs),
-                                                      (C.c_int64 * k)(*[p.numel() for p in params]), (C.c_int32 * k)(*[int(s) for s in steps]),
-                                                      (C.c_double * k)(*[float(x) for x in lrs]), float(beta1), float(beta2), float(eps),
-                                                      _ptr(live_blocks), rows, _stream_of(device)), 'fgs_adam_step_multi')
+        self._check(self.lib.fgs_adam_step_multi_quiet(k, arr(grads), arr(params), arr(exp_avgs), arr(exp_avg_sqs),
+                                                       (C.c_int64 * k)(*[p.numel() for p in params]), (C.c_int32 * k)(*[int(s) for s in steps]),
+                                                       (C.c_double * k)(*[float(x) for x in lrs]), float(beta1), float(beta2), float(eps),
+                                                       _ptr(live_blocks), rows, _ptr(quiet_blocks), _stream_of(device)), 'fgs_adam_step_multi')
+
+    def adam_quiet_scan(self, exp_avgs, exp_avg_sqs, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 [ceil(N / 64)]: 1 where every element of both moments of the block of 64 Gaussians is zero in every group (all [N, ...], one N):
+        the `quiet_blocks` of adam_step_multi, from one streaming read of the moments (fgs_adam_quiet_scan)."""
+        k = len(exp_avgs)
+        device = self._check_params(tuple(exp_avgs) + tuple(exp_avg_sqs), ['adam moment'] * (2 * k))
+        n = exp_avgs[0].shape[0]
+        if any(t.dim() < 1 or t.shape[0] != n for t in tuple(exp_avgs) + tuple(exp_avg_sqs)) or n == 0 or any(
+                m.shape != v.shape for m, v in zip(exp_avgs, exp_avg_sqs)):
+            raise RuntimeError('adam_quiet_scan needs moment tensors that all have one row per Gaussian')
+        if out is None:
+            out = torch.empty((n + 63) // 64, dtype=torch.uint8, device=device)
+        elif out.dtype != torch.uint8 or out.device != device or not out.is_contiguous() or out.numel() != (n + 63) // 64:
+            raise RuntimeError('quiet_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the moments\' device')
+        arr = lambda ts: (C.c_void_p * k)(*[_ptr(t) for t in ts])
+        self._check(self.lib.fgs_adam_quiet_scan(k, arr(exp_avgs), arr(exp_avg_sqs), (C.c_int64 * k)(*[t.numel() for t in exp_avgs]),
+                                                 (C.c_int32 * k)(*[t.numel() // n for t in exp_avgs]), _ptr(out), _stream_of(device)),
+                    'fgs_adam_quiet_scan')
+        return out
 
     def l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2,
                  with_grad: bool = True):

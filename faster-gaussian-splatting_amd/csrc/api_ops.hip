@@ -28,15 +28,21 @@ struct LossScratch {
 
 extern "C" {
 #pragma GCC visibility push(default)
-int32_t fgs_adam_step_multi_live(int32_t n_groups, const float* const* grads, float* const* params, float* const* exp_avgs,
-                                 float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
-                                 double beta1, double beta2, double eps, const uint8_t* live_blocks, const int32_t* floats_per_gaussian,
-                                 void* stream) {
+int32_t fgs_adam_step_multi_quiet(int32_t n_groups, const float* const* grads, float* const* params, float* const* exp_avgs,
+                                  float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
+                                  double beta1, double beta2, double eps, const uint8_t* live_blocks, const int32_t* floats_per_gaussian,
+                                  uint8_t* quiet_blocks, void* stream) {
     if (n_groups < 0 || n_groups > 8) return fail(FGS_ERR_INVALID_ARGUMENT, "n_groups %d (max 8)", n_groups);
-    if (live_blocks != nullptr && floats_per_gaussian == nullptr) return fail(FGS_ERR_INVALID_ARGUMENT, "live_blocks without floats_per_gaussian");
+    if ((live_blocks != nullptr || quiet_blocks != nullptr) && floats_per_gaussian == nullptr) return fail(FGS_ERR_INVALID_ARGUMENT, "live_blocks / quiet_blocks without floats_per_gaussian");
     AdamArgs a{};
     a.live_blocks = live_blocks;
     uint32_t blocks = 0;
+    int64_t rows = -1;                  // quiet_blocks: the N all groups share
+    // the skip rests on "adam_update with g = m = v = 0 is the identity", which holds for eps > 0 (as the float the kernel sees) and finite hyperparameters
+    // only (0 / 0 and inf * 0 make the dense kernel write NaN, and the skip must not hide that); without live flags, or with a tensor beyond the kernel's
+    // 32-bit row arithmetic, nothing says which blocks receive a gradient: the flags are not used then and every one of them is cleared below (the
+    // moments become unknown)
+    bool quiet_ok = quiet_blocks != nullptr && live_blocks != nullptr;
     for (int k = 0; k < n_groups; ++k) {
         if (n_elements[k] < 0 || steps[k] < 1) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: n_elements / step", k);
         if (n_elements[k] == 0) continue;
@@ -45,15 +51,56 @@ int32_t fgs_adam_step_multi_live(int32_t n_groups, const float* const* grads, fl
         g.grad = grads[k]; g.param = params[k]; g.exp_avg = exp_avgs[k]; g.exp_avg_sq = exp_avg_sqs[k]; g.n = n_elements[k];
         g.h = adam_hyper(steps[k], lrs[k], beta1, beta2, eps);
         g.row_len = 0;
-        if (live_blocks != nullptr) {
+        if (live_blocks != nullptr || quiet_blocks != nullptr) {
             if (floats_per_gaussian[k] < 1 || n_elements[k] % floats_per_gaussian[k] != 0) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: floats_per_gaussian", k);
             if (n_elements[k] < (int64_t{1} << 32)) g.row_len = static_cast<uint32_t>(floats_per_gaussian[k]);   // 32-bit index arithmetic in the kernel
+            if (quiet_blocks != nullptr) {
+                const int64_t n = n_elements[k] / floats_per_gaussian[k];
+                if (rows >= 0 && n != rows) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: quiet_blocks needs one N for all groups (%lld vs %lld)", k, (long long)n, (long long)rows);
+                rows = n;
+            }
         }
+        quiet_ok = quiet_ok && g.row_len != 0u && g.h.eps > 0.0f && std::isfinite(g.h.eps) && std::isfinite(g.h.step_size) && std::isfinite(g.h.beta1) &&
+                   std::isfinite(g.h.beta2) && std::isfinite(g.h.bc2_sqrt_rcp);
         g.first_block = blocks;
         blocks += static_cast<uint32_t>((n_elements[k] + 1023) / 1024);
     }
     a.total_blocks = blocks;
+    if (quiet_ok) a.quiet_blocks = quiet_blocks;
+    else if (quiet_blocks != nullptr && rows > 0) FGS_HIP(hipMemsetAsync(quiet_blocks, 0, static_cast<size_t>((rows + 63) / 64), static_cast<hipStream_t>(stream)));
     { StageScope t(ST_ADAM, static_cast<hipStream_t>(stream)); FGS_HIP(launch_adam(a, static_cast<hipStream_t>(stream))); }
+    return FGS_OK;
+}
+
+int32_t fgs_adam_step_multi_live(int32_t n_groups, const float* const* grads, float* const* params, float* const* exp_avgs,
+                                 float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
+                                 double beta1, double beta2, double eps, const uint8_t* live_blocks, const int32_t* floats_per_gaussian,
+                                 void* stream) {
+    return fgs_adam_step_multi_quiet(n_groups, grads, params, exp_avgs, exp_avg_sqs, n_elements, steps, lrs, beta1, beta2, eps, live_blocks,
+                                     floats_per_gaussian, nullptr, stream);
+}
+
+int32_t fgs_adam_quiet_scan(int32_t n_groups, const float* const* exp_avgs, const float* const* exp_avg_sqs, const int64_t* n_elements,
+                            const int32_t* floats_per_gaussian, uint8_t* quiet_out, void* stream) {
+    if (n_groups < 0 || n_groups > 8) return fail(FGS_ERR_INVALID_ARGUMENT, "n_groups %d (max 8)", n_groups);
+    if (n_groups > 0 && (!exp_avgs || !exp_avg_sqs || !n_elements || !floats_per_gaussian)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL argument");
+    AdamQuietScanArgs a{};
+    int64_t rows = -1;
+    for (int k = 0; k < n_groups; ++k) {
+        if (n_elements[k] < 0 || floats_per_gaussian[k] < 1 || n_elements[k] % floats_per_gaussian[k] != 0) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: n_elements / floats_per_gaussian", k);
+        const int64_t n = n_elements[k] / floats_per_gaussian[k];
+        if (rows >= 0 && n != rows) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: all groups must have the same N (%lld vs %lld)", k, (long long)n, (long long)rows);
+        rows = n;
+        if (n > 0x7fffffff || floats_per_gaussian[k] > (1 << 20)) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: N / floats_per_gaussian out of range", k);
+        if (n == 0) continue;
+        if (!exp_avgs[k] || !exp_avg_sqs[k]) return fail(FGS_ERR_INVALID_ARGUMENT, "group %d: NULL tensor", k);
+        a.m[a.n_groups] = exp_avgs[k]; a.v[a.n_groups] = exp_avg_sqs[k]; a.row_len[a.n_groups] = static_cast<uint32_t>(floats_per_gaussian[k]);
+        ++a.n_groups;
+    }
+    if (rows <= 0) return FGS_OK;
+    if (!quiet_out) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL quiet_out");
+    a.rows = static_cast<uint32_t>(rows); a.quiet_out = quiet_out;
+    FGS_HIP(launch_adam_quiet_scan(a, static_cast<hipStream_t>(stream)));
     return FGS_OK;
 }
 

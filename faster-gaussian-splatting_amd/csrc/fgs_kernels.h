@@ -221,8 +221,15 @@ struct AdamGroup { const float* grad; float* param; float* exp_avg; float* exp_a
                    uint32_t row_len; };      // floats per Gaussian in this tensor (live_blocks only; 0: read every gradient)
 // live_blocks: [ceil(N / 64)] bytes or nullptr; 0 = the caller guarantees that the gradient rows of Gaussians 64 b .. 64 b + 63 are zero:
 // they are not read (one third of the Gaussians is invisible per view, 85 % of them in such blocks: tools/dead_blocks.py)
-struct AdamArgs { AdamGroup g[8]; int n_groups; uint32_t total_blocks; int reverse; const uint8_t* live_blocks; };
+// quiet_blocks: [ceil(N / 64)] bytes or nullptr (needs live_blocks and one N for all groups); 1 = every exp_avg / exp_avg_sq element of Gaussians
+// 64 b .. 64 b + 63 in every group == 0.0f. With a zero gradient the update is then the identity on parameter and moments: a 16-byte piece whose
+// blocks are quiet and not live is neither loaded nor stored. The kernel clears the byte of every block it reads a gradient for (1 -> 0, never back).
+struct AdamArgs { AdamGroup g[8]; int n_groups; uint32_t total_blocks; int reverse; const uint8_t* live_blocks; uint8_t* quiet_blocks; };
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s);   // K13, all groups in one launch
+// quiet_out[b] = 1 iff every moment of block b compares equal to 0.0f in every group (NaN is not zero), else 0: one streaming read of the moments.
+// rows = N; group k is [N, row_len[k]]
+struct AdamQuietScanArgs { const float* m[8]; const float* v[8]; uint32_t row_len[8]; int n_groups; uint32_t rows; uint8_t* quiet_out; };
+hipError_t launch_adam_quiet_scan(const AdamQuietScanArgs& a, hipStream_t s);
 
 struct LossArgs {                       // fused L1 + DSSIM loss and its image gradient (loss.hip)
     const float* image; const float* target;   // [3,H,W]

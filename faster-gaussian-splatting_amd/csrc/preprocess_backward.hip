@@ -824,21 +824,45 @@ template <bool NT> __device__ __forceinline__ void store4(float* p, const float4
     else *reinterpret_cast<float4*>(p) = v;
 }
 
-// Does the optimizer have to READ the gradient elements first .. last (at most four consecutive floats of the [N, L] tensor)? They cover the rows
-// first / L .. last / L, which lie in at most two consecutive blocks of 64 Gaussians. Both flagged 0: every element is a zero the backward pass wrote --
+// Does the optimizer have to READ the gradient of block b (64 Gaussians) of this tensor? Flagged 0: every element is a zero the backward pass wrote --
 // skip the read (the kernel is HBM-bound; the index arithmetic is free).
-__device__ __forceinline__ bool adam_gradient_needed(const AdamArgs& a, const AdamGroup& G, const int64_t first, const int64_t last) {
-    if (a.live_blocks == nullptr || G.row_len == 0u) return true;
-    const uint32_t r0 = static_cast<uint32_t>(first) / G.row_len, r1 = static_cast<uint32_t>(last) / G.row_len;
-    const uint32_t b0 = r0 >> 6, b1 = r1 >> 6;
-    if ((a.live_blocks[b0] | a.live_blocks[b1]) != 0) return true;
+__device__ __forceinline__ bool adam_block_gradient_needed(const AdamArgs& a, const AdamGroup& G, const uint32_t b) {
+    if (a.live_blocks[b] != 0) return true;
     // Belt and braces: the promise rests on the caller's proof that nobody touched the gradients since the backward pass,
     // and a write that bypasses the framework's bookkeeping (`.grad.data.add_(...)`, a raw-pointer kernel) cannot be seen by
     // it. One SENTINEL float per flagged-0 block and tensor (the first element of the block: the same cached 4 bytes for every
     // float4 of the block) is read anyway; anything but +-0 there -- a whole-tensor edit such as hand-written weight decay,
     // NaN / Inf -- and the block's gradients are read after all.
-    const float s0 = G.grad[(size_t)b0 * 64u * G.row_len], s1 = G.grad[(size_t)b1 * 64u * G.row_len];
-    return !(s0 == 0.0f) || !(s1 == 0.0f);
+    return !(G.grad[(size_t)b * 64u * G.row_len] == 0.0f);
+}
+
+// What to do with the elements first .. last (at most four consecutive floats of the [N, L] tensor)? They cover the rows first / L .. last / L, which lie in
+// at most two consecutive blocks of 64 Gaussians.
+//   kAdamRead : some block's gradient is needed -- the piece is read and stepped in full
+//   kAdamZero : no block's gradient is needed -- the piece is stepped with g = 0 without reading it
+//   kAdamSkip : as kAdamZero, and both blocks are QUIET (a.quiet_blocks: all moments of the block == 0.0f in every group of the launch). adam_update with
+//               g = m = v = 0 leaves m = v = +0 and p -= step_size * 0 / eps = p for eps > 0 and a finite step size (the host hands no quiet flags
+//               otherwise): the piece is neither loaded nor stored, and nothing is deferred -- memory is what the full piece would have left (+-0 aside)
+// A piece that needs a block's gradient clears that block's quiet byte, with a store only if it read a 1 (steady state: no stores).
+// Races between workgroups: skipping needs "gradient not needed", clearing needs "gradient needed", and within one tensor every piece of a block sees the
+// same live flag and the same sentinel -- so no piece of a tensor skips a block that another piece of that tensor steps on a gradient. Tensors can differ
+// only through their sentinels (one tensor edited behind the flags). A piece of an unedited tensor then reads the quiet byte as 1 or as the 0 another
+// tensor's piece just stored: it skips, or it runs kAdamZero on moments that are still all zero (its elements are written by nobody else) -- the identity
+// either way, bit for bit. A piece that runs across a block border writes +0 moments and the unchanged parameter into the quiet side: harmless, and the
+// reason quiet is defined by == 0.0f and not by the bit pattern.
+enum : int { kAdamSkip = 0, kAdamZero = 1, kAdamRead = 2 };
+__device__ __forceinline__ int adam_piece_plan(const AdamArgs& a, const AdamGroup& G, const int64_t first, const int64_t last) {
+    if (a.live_blocks == nullptr || G.row_len == 0u) return kAdamRead;
+    const uint32_t r0 = static_cast<uint32_t>(first) / G.row_len, r1 = static_cast<uint32_t>(last) / G.row_len;
+    const uint32_t b0 = r0 >> 6, b1 = r1 >> 6;
+    const bool need0 = adam_block_gradient_needed(a, G, b0), need1 = b1 == b0 ? need0 : adam_block_gradient_needed(a, G, b1);
+    if (a.quiet_blocks != nullptr) {
+        const uint8_t q0 = a.quiet_blocks[b0], q1 = b1 == b0 ? q0 : a.quiet_blocks[b1];
+        if (need0 && q0 != 0) a.quiet_blocks[b0] = 0;
+        if (b1 != b0 && need1 && q1 != 0) a.quiet_blocks[b1] = 0;
+        if (!need0 && !need1 && q0 != 0 && q1 != 0) return kAdamSkip;
+    }
+    return need0 || need1 ? kAdamRead : kAdamZero;
 }
 
 template <int U, bool NT>
@@ -852,37 +876,75 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
     const AdamGroup& G = a.g[gidx];
     const int64_t block_base = (int64_t)(blk - G.first_block) * (256 * 4 * U);
     float4 g4[U], p4[U], m4[U], v4[U];
-    bool full[U];
+    bool full[U], run[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {                       // all loads of the thread are issued before any arithmetic
         const int64_t base = block_base + ((int64_t)u * 256 + threadIdx.x) * 4;
         full[u] = base + 4 <= G.n;
+        run[u] = false;
         if (full[u]) {
-            g4[u] = adam_gradient_needed(a, G, base, base + 3) ? load4<NT>(G.grad + base) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            p4[u] = load4<NT>(G.param + base);
-            m4[u] = load4<NT>(G.exp_avg + base);
-            v4[u] = load4<NT>(G.exp_avg_sq + base);
+            const int plan = adam_piece_plan(a, G, base, base + 3);
+            run[u] = plan != kAdamSkip;
+            if (run[u]) {
+                g4[u] = plan == kAdamRead ? load4<NT>(G.grad + base) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                p4[u] = load4<NT>(G.param + base);
+                m4[u] = load4<NT>(G.exp_avg + base);
+                v4[u] = load4<NT>(G.exp_avg_sq + base);
+            }
         }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int64_t base = block_base + ((int64_t)u * 256 + threadIdx.x) * 4;
         if (full[u]) {
-            adam_update(p4[u].x, m4[u].x, v4[u].x, g4[u].x, G.h); adam_update(p4[u].y, m4[u].y, v4[u].y, g4[u].y, G.h);
-            adam_update(p4[u].z, m4[u].z, v4[u].z, g4[u].z, G.h); adam_update(p4[u].w, m4[u].w, v4[u].w, g4[u].w, G.h);
-            store4<NT>(G.param + base, p4[u]);
-            store4<NT>(G.exp_avg + base, m4[u]);
-            store4<NT>(G.exp_avg_sq + base, v4[u]);
-        } else {
-            // the tensor's last (fewer than four) floats: the same promise, or a tensor of 4 k + 1 .. 3 floats would have its tail read whatever the flags say
-            const bool need = base < G.n && adam_gradient_needed(a, G, base, G.n - 1);
-            for (int64_t e = base; e < G.n && e < base + 4; ++e) {
+            if (run[u]) {
+                adam_update(p4[u].x, m4[u].x, v4[u].x, g4[u].x, G.h); adam_update(p4[u].y, m4[u].y, v4[u].y, g4[u].y, G.h);
+                adam_update(p4[u].z, m4[u].z, v4[u].z, g4[u].z, G.h); adam_update(p4[u].w, m4[u].w, v4[u].w, g4[u].w, G.h);
+                store4<NT>(G.param + base, p4[u]);
+                store4<NT>(G.exp_avg + base, m4[u]);
+                store4<NT>(G.exp_avg_sq + base, v4[u]);
+            }
+        } else if (base < G.n) {
+            // the tensor's last (fewer than four) floats: the same plan, or a tensor of 4 k + 1 .. 3 floats would have its tail read and stepped whatever the flags say
+            const int plan = adam_piece_plan(a, G, base, G.n - 1);
+            for (int64_t e = base; plan != kAdamSkip && e < G.n; ++e) {
                 float pp = G.param[e], mm = G.exp_avg[e], vv = G.exp_avg_sq[e];
-                adam_update(pp, mm, vv, need ? G.grad[e] : 0.0f, G.h);
+                adam_update(pp, mm, vv, plan == kAdamRead ? G.grad[e] : 0.0f, G.h);
                 G.param[e] = pp; G.exp_avg[e] = mm; G.exp_avg_sq[e] = vv;
             }
         }
     }
+}
+
+// ---- quiet scan: quiet_out[b] = "every moment of block b is zero", for a caller that cannot prove its flags current (once per invalidation, never per step) ----
+// One workgroup of 256 per block of 64 Gaussians: per group the block's 64 L floats of exp_avg and of exp_avg_sq are contiguous and start on a multiple of
+// 256 bytes behind the tensor's base -- 16-byte loads where the base is 16-byte aligned, scalar loads for the ragged block's tail and unaligned tensors.
+__global__ void __launch_bounds__(256) adam_quiet_scan_kernel(const AdamQuietScanArgs a) {
+    const uint32_t b = blockIdx.x;
+    const uint32_t rows = min(64u, a.rows - b * 64u);
+    bool zero = true;
+    for (int k = 0; k < a.n_groups; ++k) {
+        const size_t first = (size_t)b * 64u * a.row_len[k];
+        const uint32_t len = rows * a.row_len[k];
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            const float* t = (w == 0 ? a.m[k] : a.v[k]) + first;
+            const uint32_t vec = (reinterpret_cast<uintptr_t>(t) & 15u) == 0 ? len >> 2 : 0u;
+            for (uint32_t i = threadIdx.x; i < vec; i += 256u) {
+                const float4 x = load_float4_nt(t + 4u * i);
+                zero = zero && x.x == 0.0f && x.y == 0.0f && x.z == 0.0f && x.w == 0.0f;
+            }
+            for (uint32_t e = 4u * vec + threadIdx.x; e < len; e += 256u) zero = zero && t[e] == 0.0f;
+        }
+    }
+    const int all_zero = __syncthreads_and(zero ? 1 : 0);
+    if (threadIdx.x == 0) a.quiet_out[b] = all_zero ? 1 : 0;
+}
+
+hipError_t launch_adam_quiet_scan(const AdamQuietScanArgs& a, hipStream_t s) {
+    if (a.rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(adam_quiet_scan_kernel, dim3((a.rows + 63u) / 64u), dim3(256), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_adam(const AdamArgs& a_in, hipStream_t s) {

@@ -204,6 +204,22 @@ int32_t fgs_adam_step_multi_live(int32_t n_groups, const float* const* grads, fl
                                  float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
                                  double beta1, double beta2, double eps, const uint8_t* live_blocks, const int32_t* floats_per_gaussian,
                                  void* stream);
+/* The same with the caller's per-block QUIET flags (device, [ceil(N / 64)] bytes, owned by the optimizer; all groups [N, ...] with ONE N, else
+ * FGS_ERR_INVALID_ARGUMENT). quiet_blocks[b] = 1 promises that every exp_avg / exp_avg_sq element of Gaussians 64 b .. 64 b + 63 compares equal to 0.0f
+ * in every group of the call; 0 promises nothing. A block that is quiet and whose gradient is not needed (live_blocks 0, sentinel +-0) is neither read
+ * nor written: with g = m = v = 0 the update is the identity, so memory is bit for bit what fgs_adam_step_multi_live leaves (+-0 aside). The call
+ * clears the byte of every block it reads a gradient for and never sets one; fgs_adam_quiet_scan (re)creates the flags. The flags are not used, and all
+ * of them are CLEARED (a memset in front of the launch), when the identity cannot be relied on or nothing says which blocks get a gradient: live_blocks
+ * NULL, eps <= 0 (as a float) or not finite, a step size or beta that is not finite, a tensor of 2^32 elements or more. NULL = fgs_adam_step_multi_live. */
+int32_t fgs_adam_step_multi_quiet(int32_t n_groups, const float* const* grads, float* const* params, float* const* exp_avgs,
+                                  float* const* exp_avg_sqs, const int64_t* n_elements, const int32_t* steps, const double* lrs,
+                                  double beta1, double beta2, double eps, const uint8_t* live_blocks, const int32_t* floats_per_gaussian,
+                                  uint8_t* quiet_blocks, void* stream);
+/* quiet_out[b] = 1 exactly when every element of rows 64 b .. 64 b + 63 of every exp_avgs[k] and exp_avg_sqs[k] compares equal to 0.0f (-0 is zero,
+ * NaN is not), else 0: one streaming read of the moments, for a caller whose flags may be stale (moments replaced or edited by someone else). Arrays
+ * are [host], length n_groups <= 8; all groups must have the same N = n_elements[k] / floats_per_gaussian[k], else FGS_ERR_INVALID_ARGUMENT. */
+int32_t fgs_adam_quiet_scan(int32_t n_groups, const float* const* exp_avgs, const float* const* exp_avg_sqs, const int64_t* n_elements,
+                            const int32_t* floats_per_gaussian, uint8_t* quiet_out, void* stream);
 
 /* Fused backward + Adam (the reference's FasterGSFused branch, README.md:37; not in /root/reference -- defined here as
  * "equal to fgs_backward followed by FusedAdam.step() on all six groups"). Gradients are never
