@@ -85,7 +85,7 @@ class async_forward_scope:
 # reference count of the view, not of its storage) and clones it otherwise -- 708 MB per iteration at 3 M Gaussians. A match needs the same address, the same shape and an unchanged version counter (views share the arena's: any
 # in-place edit -- accumulation of a second backward, clipping, scaling -- shows). Anything else takes the ordinary path; results are
 # bit-identical either way. Writes the version counter does not see (`.grad.data.add_(...)`, raw pointers) are the kernel's business: it reads
-# one sentinel float per flagged-0 block and tensor and, unless that is +-0, the block's gradients after all (csrc/preprocess_backward.hip).
+# one sentinel float per flagged-0 block and tensor and, unless that is +-0, the block's gradients after all (csrc/adam.hip).
 # The registry holds ONE registration per model, keyed by the address of the `means` tensor of the pass (two models in one process do not evict
 # each other's registration; a model's next backward pass replaces its own). An optimizer names the parameters it owns when it asks.
 _LIVE = {'enabled': True, 'slots': {}, 'matched': 0, 'missed': 0}

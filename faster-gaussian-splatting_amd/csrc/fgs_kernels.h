@@ -292,7 +292,7 @@ hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s);
 size_t morton_temp_bytes(uint32_t n);
 hipError_t run_morton_order(const float* means, const float* lo, const float* hi, int64_t* order_out, uint32_t n, void* temp, size_t temp_bytes, hipStream_t s);
 
-FGS_SWITCH(g_adam_reverse, 1);                                               // option 8: reversed workgroup order (preprocess_backward.hip)
+FGS_SWITCH(g_adam_reverse, 1);                                               // option 8: reversed workgroup order (adam.hip)
 FGS_SWITCH(g_adam_nontemporal, 1);                                           // option 2: non-temporal loads / stores
 FGS_SWITCH(g_adam_unroll, 1);                                                // option 1: 1, 2 or 4 float4 pieces per thread
 #ifdef FGS_DEV_SWITCHES

@@ -15,20 +15,11 @@
 //    torch::zeros fills (rasterization_api.cu:127-134, 256 B per Gaussian).
 //  * fused mode never materialises the 59-float gradient: Adam is applied in registers. Invisible Gaussians still
 //    decay their moments and move by momentum (reference: dense zero grads, adam.py:16).
-#include "fgs_kernels.h"
-#include <fgs_wave.h>
+// K13 itself, the optimizer over materialised gradients, is adam.hip; the update and its 16-byte piece are shared through fgs_adam.h.
+#include "fgs_adam.h"
+#include <type_traits>
 
 namespace fgs {
-
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, const float g, const AdamHyper& h) {   // adam.cu:22-33
-    const float gsq = g * g;
-    const float m1 = fmaf(h.beta1, m - g, g);
-    const float m2 = fmaf(h.beta2, v - gsq, gsq);
-    const float denom = sqrtf(m2) * h.bc2_sqrt_rcp + h.eps;
-    p -= h.step_size * m1 / denom;
-    m = m1;
-    v = m2;
-}
 
 // fused mode: the 14 small floats of a Gaussian (kernel group order means 3, sh0 3, opacity 1, scales 3, rotations 4) and
 // their two Adam moments are requested at kernel entry, so the 42 loads are in flight while the gradient is computed.
@@ -101,9 +92,7 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
             for (int k = 0; k < 4; ++k) q[k] = FUSED ? st_p[10 + k] : a.rotations[4 * (size_t)i + k];
         }
         reached = true;
-        const float* const accp = rec;
-        constexpr size_t es = 1;
-        const float gcol[3] = {accp[6 * es], accp[7 * es], accp[8 * es]};
+        const float gcol[3] = {rec[6], rec[7], rec[8]};
         if (KEEP_DIR) { gcol_out[0] = gcol[0]; gcol_out[1] = gcol[1]; gcol_out[2] = gcol[2]; }
 
         // ---- SH backward w.r.t. sh0 and the view direction (sh_utils.cuh:84-153) ----
@@ -163,11 +152,11 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
         const float aa = ea * ea, bb = eb * eb, cc = ec * ec, ac = ea * ec, ab = ea * eb, bc = eb * ec;
         const float det = ac - bb;
         const float det_rcp_sq = 1.0f / (det * det);
-        const float gcx = accp[2 * es], gcy = accp[3 * es], gcz = accp[4 * es];
+        const float gcx = rec[2], gcy = rec[3], gcz = rec[4];
         const float dcov_x = det_rcp_sq * (2.0f * bc * gcy - cc * gcx - bb * gcz);     // kb:130-134
         const float dcov_y = det_rcp_sq * (bc * gcx - (ac + bb) * gcy + ab * gcz);
         const float dcov_z = det_rcp_sq * (2.0f * ab * gcy - bb * gcx - aa * gcz);
-        float d_opacity = accp[5 * es];
+        float d_opacity = rec[5];
         if (cam.proper_aa) {                                                           // kb:137-145 (cov2d branch off, cfg:12)
             const float opacity = sigmoid_f(FUSED ? st_p[6] : a.opacities[i]);
             const float det_raw = P.a_raw * P.c_raw - bb;
@@ -192,7 +181,7 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
         const float dj22 = cam.r2[0] * djw2[0] + cam.r2[1] * djw2[1] + cam.r2[2] * djw2[2];
         const float dj13 = cam.r3[0] * djw1[0] + cam.r3[1] * djw1[1] + cam.r3[2] * djw1[2];
         const float dj23 = cam.r3[0] * djw2[0] + cam.r3[1] * djw2[1] + cam.r3[2] * djw2[2];
-        const float gm2x = accp[0], gm2y = accp[es];
+        const float gm2x = rec[0], gm2y = rec[1];
         if (a.densification_info != nullptr) {                                         // kb:197-201 (the count of visible views: above)
             const float nx = 0.5f * (gm2x * cam.width), ny = 0.5f * (gm2y * cam.height);
             a.densification_info[n + i] += sqrtf(nx * nx + ny * ny);
@@ -274,6 +263,29 @@ __global__ void __launch_bounds__(kPreprocessBackwardBlock) preprocess_backward_
         }
 }
 
+// ---- what the wave-per-64-Gaussians kernels share ---------------------------------------------------------------------
+// Workgroups of 256. Wave wv of a workgroup owns the Gaussians first .. first + n_here - 1, one per lane, and with them a CONTIGUOUS run of the
+// [N, R, 3] tensors: count floats from element base on (64 * R * 12 bytes per wave: 16-byte aligned iff the tensor is). A wave with first >= n
+// has nothing to do and returns at once (wave-uniform); n_here and count mean something only for the others.
+struct WaveBlock { uint32_t R, lane, wv, first, n_here, count; size_t base; };
+template <int RT> __device__ __forceinline__ WaveBlock wave_block(const uint32_t n, const uint32_t total_sh_rest) {
+    WaveBlock w;
+    w.R = RT > 0 ? static_cast<uint32_t>(RT) : total_sh_rest;
+    w.lane = lane_id(); w.wv = threadIdx.x >> 6;
+    w.first = blockIdx.x * 256u + w.wv * kWave;
+    w.n_here = n - w.first < kWave ? n - w.first : kWave;
+    w.count = w.n_here * w.R * 3u;
+    w.base = (size_t)w.first * w.R * 3u;
+    return w;
+}
+
+// The 15 basis values of a view direction: zeros if `on` is false, and for the degrees above the active one (they keep a zero gradient)
+__device__ __forceinline__ void lane_sh_basis(float (&B)[15], const bool on, const float x, const float y, const float z, const unsigned active) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) B[k] = 0.0f;
+    if (on) sh_basis(x, y, z, active, B);
+}
+
 // ---- the wave's SH-rest gradient block, kept FACTORED in LDS ---------------------------------------------------------
 // The gradient of sh_coefficients_rest[g][k][c] is basis_k(dir_g) * dL/dcolour_c(g) (sh_utils.cuh:90-111): 18 numbers per Gaussian
 // (3 colour gradients + 15 basis values) instead of 45 products: 4.5 KB of LDS per wave instead of 11.25 KB, and the product is formed when
@@ -287,9 +299,7 @@ constexpr uint32_t kShFactorFloats = kWave * kShFactorStride;
 __device__ __forceinline__ void put_sh_factors(float* const slice, const uint32_t lane, const bool reached, const float (&dir)[3],
                                                const float (&gcol)[3], const int active_sh_bases) {
     float B[15];
-#pragma unroll
-    for (int k = 0; k < 15; ++k) B[k] = 0.0f;                         // degrees above the active one keep a zero gradient
-    if (reached && active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], active_sh_bases, B);
+    lane_sh_basis(B, reached && active_sh_bases > 1, dir[0], dir[1], dir[2], active_sh_bases);
     float* const mine = slice + lane * kShFactorStride;
     mine[0] = gcol[0]; mine[1] = gcol[1]; mine[2] = gcol[2];           // zeros for an invisible or unreached Gaussian
 #pragma unroll
@@ -338,87 +348,82 @@ constexpr int kFusedUnroll = FGS_FUSED_UNROLL;          // 16-byte pieces of eac
 #ifndef FGS_FUSED_WAVES
 #define FGS_FUSED_WAVES 3
 #endif
-template <int RT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FGS_FUSED_WAVES, FGS_FUSED_WAVES)))
-fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) {
-    __shared__ __attribute__((aligned(16))) float s_grad[256 / kWave][kShFactorFloats];   // >= the 14 x 64 floats phase A stages per array
-    const uint32_t R = RT > 0 ? static_cast<uint32_t>(RT) : sh.total_sh_rest;
-    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-    const uint32_t first = blockIdx.x * 256u + wv * kWave;            // first Gaussian of this wave
-    if (first >= a.n) return;                                         // wave-uniform
-    const uint32_t i = first + lane;
-    const bool in_range = i < a.n;
-    float* const slice = s_grad[wv];                                  // the wave's LDS slice: phase A staging now, the SH-rest gradient block later
-    const uint32_t n_here = a.n - first < kWave ? a.n - first : kWave;   // Gaussians of this wave
-    const bool whole = a.vector_ok != 0 && n_here == kWave;           // 16-byte accesses need 16-byte aligned tensors (checked at launch)
-
-    // ---- phase A: the 14 small floats of parameters and both moments. A wave's 64 x w floats of a group are contiguous: they come in (and
-    // go out) as ONE coalesced 16-byte access per lane and pass through LDS, instead of w scalar accesses per lane at a stride of 4 w bytes --
-    // 42 loads + 42 stores per lane before, more memory instructions than phase B issues for three times the data. ----
-    // The parameters come first (the gradient needs them); the moments are requested after the gradient is formed, so 28 registers are not
-    // held across gaussian_backward, and every array passes through the same 3.5 KB of the slice. Round 3, one box: 0.850 -> 0.812 ms
-    // (profiles/archive/r03_ab_fused_factored.txt; 3 or 4 waves per SIMD measure the same, 5 spills; requesting phase B's first pieces before the
-    // gradient, or double-buffering phase B, measured slower at every depth tried).
-    constexpr int kLanes[5] = {48, 48, 16, 48, 64};                   // 64 w / 4 float4 pieces
-    float st_p[14], st_m[14], st_v[14];
-    const uint32_t ic = in_range ? i : a.n - 1u;                      // partial wave: out-of-range lanes shadow the last Gaussian (loads only)
+// Phase A moves one array at a time -- the five group tensors of the parameters, of exp_avg or of exp_avg_sq -- between global memory and the 14
+// registers of every lane. whole (a full wave of 16-byte aligned tensors): a wave's 64 x w floats of a group are contiguous, so they come in (and go
+// out) as ONE coalesced 16-byte access per lane and pass through the wave's LDS slice; otherwise w scalar accesses per lane.
+constexpr int kStageLanes[5] = {48, 48, 16, 48, 64};                  // 64 w / 4 float4 pieces
+__device__ __forceinline__ void stage_request(float4 (&in)[5], float* const (&src)[5], const bool whole, const WaveBlock& w) {
+    if (!whole) return;                                               // stage_in gathers
+#pragma unroll
+    for (int grp = 0; grp < 5; ++grp)
+        if (w.lane < static_cast<uint32_t>(kStageLanes[grp])) in[grp] = load_float4_nt(src[grp] + (size_t)w.first * kGroupWidth[grp] + 4u * w.lane);
+}
+// ic: the lane's Gaussian; the out-of-range lanes of a partial wave shadow the last one (loads only)
+__device__ __forceinline__ void stage_in(float (&st)[14], float* const (&src)[5], const float4 (&in)[5], const bool whole, const uint32_t ic,
+                                         const WaveBlock& w, float* const slice) {
     if (whole) {
-        float4 in[5];
 #pragma unroll
         for (int grp = 0; grp < 5; ++grp)
-            if (lane < static_cast<uint32_t>(kLanes[grp])) in[grp] = load_float4_nt(a.p[grp] + (size_t)first * kGroupWidth[grp] + 4u * lane);
-#pragma unroll
-        for (int grp = 0; grp < 5; ++grp)
-            if (lane < static_cast<uint32_t>(kLanes[grp])) *reinterpret_cast<float4*>(slice + kGroupOffset[grp] * kWave + 4u * lane) = in[grp];
+            if (w.lane < static_cast<uint32_t>(kStageLanes[grp])) *reinterpret_cast<float4*>(slice + kGroupOffset[grp] * kWave + 4u * w.lane) = in[grp];
         wave_lds_fence();
 #pragma unroll
         for (int grp = 0; grp < 5; ++grp)
 #pragma unroll
-            for (int k = 0; k < kGroupWidth[grp]; ++k) st_p[kGroupOffset[grp] + k] = slice[kGroupOffset[grp] * kWave + lane * kGroupWidth[grp] + k];
-        wave_lds_fence();                                             // the moments overwrite the slice
+            for (int k = 0; k < kGroupWidth[grp]; ++k) st[kGroupOffset[grp] + k] = slice[kGroupOffset[grp] * kWave + w.lane * kGroupWidth[grp] + k];
+        wave_lds_fence();                                             // the next array overwrites the slice
     } else {
 #pragma unroll
         for (int grp = 0; grp < 5; ++grp)
 #pragma unroll
-            for (int k = 0; k < kGroupWidth[grp]; ++k) st_p[kGroupOffset[grp] + k] = a.p[grp][(size_t)ic * kGroupWidth[grp] + k];
+            for (int k = 0; k < kGroupWidth[grp]; ++k) st[kGroupOffset[grp] + k] = src[grp][(size_t)ic * kGroupWidth[grp] + k];
     }
+}
+__device__ __forceinline__ void stage_out(float* const (&dst)[5], const float (&st)[14], const bool whole, const WaveBlock& w, float* const slice) {
+    if (whole) {
+#pragma unroll
+        for (int grp = 0; grp < 5; ++grp)
+#pragma unroll
+            for (int k = 0; k < kGroupWidth[grp]; ++k) slice[kGroupOffset[grp] * kWave + w.lane * kGroupWidth[grp] + k] = st[kGroupOffset[grp] + k];
+        wave_lds_fence();
+#pragma unroll
+        for (int grp = 0; grp < 5; ++grp)
+            if (w.lane < static_cast<uint32_t>(kStageLanes[grp]))
+                store_float4_nt(dst[grp] + (size_t)w.first * kGroupWidth[grp] + 4u * w.lane, *reinterpret_cast<const float4*>(slice + kGroupOffset[grp] * kWave + 4u * w.lane));
+        wave_lds_fence();                                             // the slice is rewritten by the next array, then by the SH-rest factors
+    }
+}
+
+template <int RT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FGS_FUSED_WAVES, FGS_FUSED_WAVES)))
+fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) {
+    __shared__ __attribute__((aligned(16))) float s_grad[256 / kWave][kShFactorFloats];   // >= the 14 x 64 floats phase A stages per array
+    const WaveBlock w = wave_block<RT>(a.n, sh.total_sh_rest);
+    if (w.first >= a.n) return;
+    const uint32_t i = w.first + w.lane;
+    const bool in_range = i < a.n;
+    float* const slice = s_grad[w.wv];                                // the wave's LDS slice: phase A staging now, the SH-rest gradient block later
+    const bool whole = a.vector_ok != 0 && w.n_here == kWave;         // 16-byte accesses need 16-byte aligned tensors (checked at launch)
+
+    // ---- phase A: the 14 small floats of parameters and both moments (stage_request / stage_in / stage_out), instead of w scalar accesses per
+    // lane at a stride of 4 w bytes -- 42 loads + 42 stores per lane before, more memory instructions than phase B issues for three times the data. ----
+    // The parameters come first (the gradient needs them); the moments are requested after the gradient is formed, so 28 registers are not
+    // held across gaussian_backward, and every array passes through the same 3.5 KB of the slice. Round 3, one box: 0.850 -> 0.812 ms
+    // (profiles/archive/r03_ab_fused_factored.txt; 3 or 4 waves per SIMD measure the same, 5 spills; requesting phase B's first pieces before the
+    // gradient, or double-buffering phase B, measured slower at every depth tried).
+    float st_p[14], st_m[14], st_v[14];
+    float4 in_p[5], in_m[5], in_v[5];
+    const uint32_t ic = in_range ? i : a.n - 1u;
+    stage_request(in_p, a.p, whole, w);
+    stage_in(st_p, a.p, in_p, whole, ic, w, slice);
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
     bool reached = false;
 #pragma unroll
     for (int k = 0; k < 14; ++k) grad[k] = 0.0f;
     if (in_range) gaussian_backward<true, false, true>(a, i, st_p, grad, dir, gcol, reached);
-    if (whole) {
-        float4 in[2][5];
-#pragma unroll
-        for (int arr = 0; arr < 2; ++arr)
-#pragma unroll
-            for (int grp = 0; grp < 5; ++grp)
-                if (lane < static_cast<uint32_t>(kLanes[grp]))
-                    in[arr][grp] = load_float4_nt((arr == 0 ? a.m[grp] : a.v[grp]) + (size_t)first * kGroupWidth[grp] + 4u * lane);
-#pragma unroll
-        for (int arr = 0; arr < 2; ++arr) {
-#pragma unroll
-            for (int grp = 0; grp < 5; ++grp)
-                if (lane < static_cast<uint32_t>(kLanes[grp])) *reinterpret_cast<float4*>(slice + kGroupOffset[grp] * kWave + 4u * lane) = in[arr][grp];
-            wave_lds_fence();
-#pragma unroll
-            for (int grp = 0; grp < 5; ++grp)
-#pragma unroll
-                for (int k = 0; k < kGroupWidth[grp]; ++k) {
-                    const float x = slice[kGroupOffset[grp] * kWave + lane * kGroupWidth[grp] + k];
-                    if (arr == 0) st_m[kGroupOffset[grp] + k] = x; else st_v[kGroupOffset[grp] + k] = x;
-                }
-            wave_lds_fence();
-        }
-    } else {
-#pragma unroll
-        for (int grp = 0; grp < 5; ++grp)
-#pragma unroll
-            for (int k = 0; k < kGroupWidth[grp]; ++k) {
-                const size_t e = (size_t)ic * kGroupWidth[grp] + k;
-                st_m[kGroupOffset[grp] + k] = a.m[grp][e]; st_v[kGroupOffset[grp] + k] = a.v[grp][e];
-            }
-    }
+    stage_request(in_m, a.m, whole, w);                               // both moments are requested before either is consumed
+    stage_request(in_v, a.v, whole, w);
+    stage_in(st_m, a.m, in_m, whole, ic, w, slice);
+    stage_in(st_v, a.v, in_v, whole, ic, w, slice);
     if (in_range) {
 #pragma unroll
         for (int grp = 0; grp < 5; ++grp)
@@ -426,69 +431,43 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
             for (int k = 0; k < kGroupWidth[grp]; ++k) {
                 const int o = kGroupOffset[grp] + k;
                 adam_update(st_p[o], st_m[o], st_v[o], grad[o], a.h[grp]);
-                if (!whole) {
+                if (!whole) {                                         // scalar path: stored here, not in stage_out -- 42 values held to the end cost 4 registers
                     const size_t e = (size_t)i * kGroupWidth[grp] + k;
                     a.p[grp][e] = st_p[o]; a.m[grp][e] = st_m[o]; a.v[grp][e] = st_v[o];
                 }
             }
     }
-    if (whole) {
-#pragma unroll
-        for (int arr = 0; arr < 3; ++arr) {
-#pragma unroll
-            for (int grp = 0; grp < 5; ++grp)
-#pragma unroll
-                for (int k = 0; k < kGroupWidth[grp]; ++k) {
-                    const int o = kGroupOffset[grp] + k;
-                    slice[kGroupOffset[grp] * kWave + lane * kGroupWidth[grp] + k] = arr == 0 ? st_p[o] : arr == 1 ? st_m[o] : st_v[o];
-                }
-            wave_lds_fence();
-#pragma unroll
-            for (int grp = 0; grp < 5; ++grp) {
-                float* const dst = (arr == 0 ? a.p[grp] : arr == 1 ? a.m[grp] : a.v[grp]) + (size_t)first * kGroupWidth[grp];
-                if (lane < static_cast<uint32_t>(kLanes[grp]))
-                    store_float4_nt(dst + 4u * lane, *reinterpret_cast<const float4*>(slice + kGroupOffset[grp] * kWave + 4u * lane));
-            }
-            wave_lds_fence();                                         // the slice is rewritten by the next array, then by the SH-rest factors
-        }
-    }
-    if (R == 0) return;
+    stage_out(a.p, st_p, whole, w, slice);
+    stage_out(a.m, st_m, whole, w, slice);
+    stage_out(a.v, st_v, whole, w, slice);
+    if (w.R == 0) return;
 
     // ---- the wave's SH-rest gradient factors -> LDS (skipped when K11 reached no Gaussian of the wave: the block is zero) ----
     const bool any_reached = wave_ballot(reached) != 0;
     if (any_reached) {
-        put_sh_factors(slice, lane, reached, dir, gcol, sh.active_sh_bases);
+        put_sh_factors(slice, w.lane, reached, dir, gcol, sh.active_sh_bases);
         wave_lds_fence();
     }
 
     // ---- phase B: Adam over the wave's contiguous block, 3 streams x kFusedUnroll pieces in flight per lane ----
-    const uint32_t count = (a.n - first < kWave ? a.n - first : kWave) * R * 3u;      // floats this wave owns
-    const size_t base = (size_t)first * R * 3u;                                        // 64 * R * 12 bytes per wave: 16-byte aligned
-    float* const P = sh.p + base; float* const M = sh.m + base; float* const V = sh.v + base;
-    for (uint32_t e0 = 4u * lane; e0 < count; e0 += 4u * kWave * kFusedUnroll) {
-        float4 p4[kFusedUnroll], m4[kFusedUnroll], v4[kFusedUnroll];
+    float* const P = sh.p + w.base; float* const M = sh.m + w.base; float* const V = sh.v + w.base;
+    for (uint32_t e0 = 4u * w.lane; e0 < w.count; e0 += 4u * kWave * kFusedUnroll) {
+        AdamPiece piece[kFusedUnroll];
         bool full[kFusedUnroll];
 #pragma unroll
         for (int u = 0; u < kFusedUnroll; ++u) {
             const uint32_t e = e0 + 4u * kWave * static_cast<uint32_t>(u);
-            full[u] = e + 4u <= count && a.vector_ok != 0;                             // 16-byte pieces need 16-byte aligned tensors (checked at launch)
-            if (full[u]) { p4[u] = load_float4_nt(P + e); m4[u] = load_float4_nt(M + e); v4[u] = load_float4_nt(V + e); }
+            full[u] = e + 4u <= w.count && a.vector_ok != 0;                           // 16-byte pieces need 16-byte aligned tensors (checked at launch)
+            if (full[u]) piece[u].load(P + e, M + e, V + e);
         }
 #pragma unroll
         for (int u = 0; u < kFusedUnroll; ++u) {
             const uint32_t e = e0 + 4u * kWave * static_cast<uint32_t>(u);
-            if (full[u]) {
-                const float4 g = any_reached ? sh_rest_gradient_piece<RT>(slice, e, R) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                adam_update(p4[u].x, m4[u].x, v4[u].x, g.x, sh.h); adam_update(p4[u].y, m4[u].y, v4[u].y, g.y, sh.h);
-                adam_update(p4[u].z, m4[u].z, v4[u].z, g.z, sh.h); adam_update(p4[u].w, m4[u].w, v4[u].w, g.w, sh.h);
-                store_float4_nt(P + e, p4[u]); store_float4_nt(M + e, m4[u]); store_float4_nt(V + e, v4[u]);
-            } else if (e < count) {                                                    // ragged tail of the last wave (< 4 floats), or unaligned tensors
-                for (uint32_t j = e; j < count && j < e + 4u; ++j) {
-                    float pp = P[j], mm = M[j], vv = V[j];
-                    adam_update(pp, mm, vv, any_reached ? sh_rest_gradient_at<RT>(slice, j, R) : 0.0f, sh.h);
-                    P[j] = pp; M[j] = mm; V[j] = vv;
-                }
-            }
+            if (full[u])
+                piece[u].step(P + e, M + e, V + e, any_reached ? sh_rest_gradient_piece<RT>(slice, e, w.R) : make_float4(0.0f, 0.0f, 0.0f, 0.0f), sh.h);
+            else if (e < w.count)                                                      // ragged tail of the last wave (< 4 floats), or unaligned tensors
+                adam_scalar_tail(P, M, V, e, w.count < e + 4u ? w.count : e + 4u, sh.h,
+                                 [&](const uint32_t j) { return any_reached ? sh_rest_gradient_at<RT>(slice, j, w.R) : 0.0f; });
         }
     }
 }
@@ -504,11 +483,9 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
 template <int RT>
 __global__ void __launch_bounds__(256) backward_gradients_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) {
     __shared__ __attribute__((aligned(16))) float s_grad[256 / kWave][kWave * 15 * 3];
-    const uint32_t R = RT > 0 ? static_cast<uint32_t>(RT) : sh.total_sh_rest;
-    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-    const uint32_t first = blockIdx.x * 256u + wv * kWave;
-    if (first >= a.n) return;                                         // wave-uniform
-    const uint32_t i = first + lane;
+    const WaveBlock w = wave_block<RT>(a.n, sh.total_sh_rest);
+    if (w.first >= a.n) return;
+    const uint32_t i = w.first + w.lane;
     const bool in_range = i < a.n;
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
     const float unused[14] = {};
@@ -530,26 +507,23 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
 #endif
             }
     }
-    float* const slice = s_grad[wv];
+    float* const slice = s_grad[w.wv];
     const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
-    if (a.live_blocks != nullptr && lane == 0) a.live_blocks[first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
-    if (a.reached_blocks != nullptr && lane == 0) a.reached_blocks[first >> 6] = any_reached ? 1 : 0;   // 0: all 59 floats of every row of the block were written as +0
-    if (R == 0) return;
+    if (a.live_blocks != nullptr && w.lane == 0) a.live_blocks[w.first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
+    if (a.reached_blocks != nullptr && w.lane == 0) a.reached_blocks[w.first >> 6] = any_reached ? 1 : 0;   // 0: all 59 floats of every row of the block were written as +0
+    if (w.R == 0) return;
     if (any_reached) {                                                 // a wave K11 reached no Gaussian of writes its SH-rest block as zeros
         float B[15];
-#pragma unroll
-        for (int k = 0; k < 15; ++k) B[k] = 0.0f;
-        if (reached && sh.active_sh_bases > 1) sh_basis(dir[0], dir[1], dir[2], sh.active_sh_bases, B);
-        float* const mine = slice + lane * R * 3u;
+        lane_sh_basis(B, reached && sh.active_sh_bases > 1, dir[0], dir[1], dir[2], sh.active_sh_bases);
+        float* const mine = slice + w.lane * w.R * 3u;
 #pragma unroll
         for (int k = 0; k < 15; ++k)
-            if (static_cast<uint32_t>(k) < R) { mine[3 * k] = B[k] * gcol[0]; mine[3 * k + 1] = B[k] * gcol[1]; mine[3 * k + 2] = B[k] * gcol[2]; }
+            if (static_cast<uint32_t>(k) < w.R) { mine[3 * k] = B[k] * gcol[0]; mine[3 * k + 1] = B[k] * gcol[1]; mine[3 * k + 2] = B[k] * gcol[2]; }
         wave_lds_fence();
     }
-    const uint32_t count = (a.n - first < kWave ? a.n - first : kWave) * R * 3u;
-    float* const out = sh.grad_sh_rest + (size_t)first * R * 3u;
-    for (uint32_t e = 4u * lane; e < count; e += 4u * kWave) {
-        if (e + 4u <= count && a.vector_ok) {                          // 16-byte stores need a 16-byte aligned gradient tensor (checked at launch)
+    float* const out = sh.grad_sh_rest + w.base;
+    for (uint32_t e = 4u * w.lane; e < w.count; e += 4u * kWave) {
+        if (e + 4u <= w.count && a.vector_ok) {                        // 16-byte stores need a 16-byte aligned gradient tensor (checked at launch)
             const float4 g = any_reached ? *reinterpret_cast<const float4*>(slice + e) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #if FGS_K12_NT_STORES
             store_float4_nt(out + e, g);
@@ -557,35 +531,38 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
             *reinterpret_cast<float4*>(out + e) = g;
 #endif
         } else {
-            for (uint32_t j = e; j < count && j < e + 4u; ++j) out[j] = any_reached ? slice[j] : 0.0f;
+            for (uint32_t j = e; j < w.count && j < e + 4u; ++j) out[j] = any_reached ? slice[j] : 0.0f;
         }
     }
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The SH-rest kernels come in two instantiations: RT = 15 (every degree present: the divisions by R are by a constant) and 0 (R read from the
+// arguments). launch(rt) starts the one for decltype(rt)::value; more than 15 coefficients per channel fit none of them.
+template <class Launch> static hipError_t dispatch_sh_rest(const uint32_t total_sh_rest, Launch launch) {
+    if (total_sh_rest > 15) return hipErrorInvalidValue;
+    if (total_sh_rest == 15) launch(std::integral_constant<int, 15>());
+    else launch(std::integral_constant<int, 0>());
+    return hipGetLastError();
+}
+
 hipError_t launch_backward_gradients(const PreprocessBackwardArgs& a_in, const ShRestArgs& sh, hipStream_t s) {
     if (a_in.n == 0) return hipSuccess;
-    if (sh.total_sh_rest > 15) return hipErrorInvalidValue;
     PreprocessBackwardArgs a = a_in;
     a.vector_ok = aligned16(sh.grad_sh_rest) ? 1 : 0;                  // a wave's block starts 64 * R * 12 bytes into the tensor: aligned iff the tensor is
     const dim3 grid((a.n + 255u) / 256u), block(256);
-    if (sh.total_sh_rest == 15) hipLaunchKernelGGL(backward_gradients_kernel<15>, grid, block, 0, s, a, sh);
-    else hipLaunchKernelGGL(backward_gradients_kernel<0>, grid, block, 0, s, a, sh);
-    return hipGetLastError();
+    return dispatch_sh_rest(sh.total_sh_rest, [&](auto rt) { hipLaunchKernelGGL(backward_gradients_kernel<decltype(rt)::value>, grid, block, 0, s, a, sh); });
 }
 
 hipError_t launch_fused_backward_adam(const PreprocessBackwardArgs& a_in, const ShRestArgs& sh, hipStream_t s) {
     if (a_in.n == 0) return hipSuccess;
-    if (sh.total_sh_rest > 15) return hipErrorInvalidValue;
     PreprocessBackwardArgs a = a_in;
     a.vector_ok = 1;
     for (int g = 0; g < 5; ++g) a.vector_ok = a.vector_ok && aligned16(a.p[g]) && aligned16(a.m[g]) && aligned16(a.v[g]);
     a.vector_ok = a.vector_ok && aligned16(sh.p) && aligned16(sh.m) && aligned16(sh.v);          // phase B: a wave's block starts 64 * R * 12 bytes in
     const dim3 grid((a.n + 255u) / 256u), block(256);
-    if (sh.total_sh_rest == 15) hipLaunchKernelGGL(fused_backward_adam_kernel<15>, grid, block, 0, s, a, sh);
-    else hipLaunchKernelGGL(fused_backward_adam_kernel<0>, grid, block, 0, s, a, sh);
-    return hipGetLastError();
+    return dispatch_sh_rest(sh.total_sh_rest, [&](auto rt) { hipLaunchKernelGGL(fused_backward_adam_kernel<decltype(rt)::value>, grid, block, 0, s, a, sh); });
 }
 
 hipError_t launch_preprocess_backward(bool fused_adam, const PreprocessBackwardArgs& a, hipStream_t s) {
@@ -625,9 +602,7 @@ __device__ __forceinline__ PairGrad pair_gradient(const ShRestArgs& a, const ShR
                            (k >= 8 && k < 15 && a.active_sh_bases > 9);
     const bool on = pair_in < n_pairs && degree_on && touched != 0;
     float B[15];
-#pragma unroll
-    for (int j = 0; j < 15; ++j) B[j] = 0.0f;
-    sh_basis(x, y, z, a.active_sh_bases, B);
+    lane_sh_basis(B, true, x, y, z, a.active_sh_bases);
     float bk = 0.0f;
 #pragma unroll
     for (int j = 0; j < 15; ++j) bk = (k == static_cast<uint32_t>(j)) ? B[j] : bk;   // select, no dynamic register indexing
@@ -642,18 +617,14 @@ __device__ __forceinline__ PairGrad pair_gradient(const ShRestArgs& a, const ShR
 // private LDS slice and leaves as fully coalesced 16-byte stores. (v1: one lane per (Gaussian, basis) pair evaluated all 15
 // basis functions to keep one -- 33 VALU instructions per output float, half VALU-bound at 0.184 ms for a 540 MB write.)
 // MULTI (sharded path): the gradient is summed over the views of the launch, colour gradients come from the accumulator records.
-// lane `lane` of a wave whose first Gaussian is `first`: the 3 * R gradient floats of Gaussian first + lane, summed over the
-// views of the launch, written to the wave's LDS slice at [lane * R * 3 ...] (the slice then holds the wave's contiguous
-// block of the [N, R, 3] tensor).
-template <int RT, bool MULTI>
-__device__ __forceinline__ void sh_rest_block_to_lds(const ShRestArgs& a, const uint32_t first, const uint32_t lane, float* slice) {
-    constexpr int kMaxRest = 15;
-    const uint32_t R = RT > 0 ? static_cast<uint32_t>(RT) : a.total_sh_rest;
-    const uint32_t gi = first + lane;
+// The lane of Gaussian w.first + w.lane: its 3 * R gradient floats, summed over the views of the launch, go to the wave's LDS slice.
+template <bool MULTI>
+__device__ __forceinline__ void sh_rest_block_to_lds(const ShRestArgs& a, const WaveBlock& w, float* slice) {
+    const uint32_t gi = w.first + w.lane;
     const bool in_range = gi < a.n;
-    float g[kMaxRest][3];
+    float g[15][3];
 #pragma unroll
-    for (int k = 0; k < kMaxRest; ++k) { g[k][0] = 0.0f; g[k][1] = 0.0f; g[k][2] = 0.0f; }
+    for (int k = 0; k < 15; ++k) { g[k][0] = 0.0f; g[k][1] = 0.0f; g[k][2] = 0.0f; }
     const int n_views = MULTI ? a.n_views : 1;
     for (int vw = 0; vw < n_views; ++vw) {
         const ShRestView& V = a.view[MULTI ? vw : 0];
@@ -662,41 +633,36 @@ __device__ __forceinline__ void sh_rest_block_to_lds(const ShRestArgs& a, const 
         float c[3];
         const float* const r = V.acc + (size_t)(MULTI ? V.slot[gi] : gi) * kAccRecordWords;       // K11's record (sharded path: through the slot table)
         c[0] = r[6]; c[1] = r[7]; c[2] = r[8];
-        float B[kMaxRest];
+        float B[15];
+        lane_sh_basis(B, a.active_sh_bases > 1, x, y, z, a.active_sh_bases);
 #pragma unroll
-        for (int k = 0; k < kMaxRest; ++k) B[k] = 0.0f;                 // degrees above the active one keep a zero gradient
-        if (a.active_sh_bases > 1) sh_basis(x, y, z, a.active_sh_bases, B);
-#pragma unroll
-        for (int k = 0; k < kMaxRest; ++k) {
+        for (int k = 0; k < 15; ++k) {
             if (!MULTI) { g[k][0] = B[k] * c[0]; g[k][1] = B[k] * c[1]; g[k][2] = B[k] * c[2]; }
             else { g[k][0] += B[k] * c[0]; g[k][1] += B[k] * c[1]; g[k][2] += B[k] * c[2]; }
         }
     }
-    float* mine = slice + lane * R * 3u;
+    float* mine = slice + w.lane * w.R * 3u;
 #pragma unroll
-    for (int k = 0; k < kMaxRest; ++k)
-        if (static_cast<uint32_t>(k) < R) { mine[3 * k] = g[k][0]; mine[3 * k + 1] = g[k][1]; mine[3 * k + 2] = g[k][2]; }
+    for (int k = 0; k < 15; ++k)
+        if (static_cast<uint32_t>(k) < w.R) { mine[3 * k] = g[k][0]; mine[3 * k + 1] = g[k][1]; mine[3 * k + 2] = g[k][2]; }
     wave_lds_fence();
 }
 
 template <int RT, bool MULTI>
 __global__ void __launch_bounds__(256) sh_rest_gradient_kernel(const ShRestArgs a) {
     __shared__ __attribute__((aligned(16))) float s_out[256 / kWave][kWave * 15 * 3];
-    const uint32_t R = RT > 0 ? static_cast<uint32_t>(RT) : a.total_sh_rest;
-    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-    const uint32_t first = (blockIdx.x * 256u + wv * kWave);         // first Gaussian of this wave
-    if (first >= a.n) return;                                         // wave-uniform
-    sh_rest_block_to_lds<RT, MULTI>(a, first, lane, s_out[wv]);
-    const uint32_t count = (a.n - first < kWave ? a.n - first : kWave) * R * 3u;      // floats this wave owns
-    float* out = a.grad_sh_rest + (size_t)first * R * 3u;                             // 64 * R * 12 bytes per wave: 16-byte aligned
+    const WaveBlock w = wave_block<RT>(a.n, a.total_sh_rest);
+    if (w.first >= a.n) return;
+    sh_rest_block_to_lds<MULTI>(a, w, s_out[w.wv]);
+    float* out = a.grad_sh_rest + w.base;
     const bool add = MULTI && a.accumulate;                                            // view batches after the first
-    for (uint32_t e = 4u * lane; e < count; e += 4u * kWave) {
-        if (e + 4u <= count) {
-            float4 v = *reinterpret_cast<const float4*>(&s_out[wv][e]);
+    for (uint32_t e = 4u * w.lane; e < w.count; e += 4u * kWave) {
+        if (e + 4u <= w.count) {
+            float4 v = *reinterpret_cast<const float4*>(&s_out[w.wv][e]);
             if (add) { const float4 o = *reinterpret_cast<const float4*>(out + e); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
             *reinterpret_cast<float4*>(out + e) = v;
         } else {
-            for (uint32_t j = e; j < count; ++j) out[j] = add ? out[j] + s_out[wv][j] : s_out[wv][j];
+            for (uint32_t j = e; j < w.count; ++j) out[j] = add ? out[j] + s_out[w.wv][j] : s_out[w.wv][j];
         }
     }
 }
@@ -706,26 +672,17 @@ __global__ void __launch_bounds__(256) sh_rest_gradient_kernel(const ShRestArgs 
 template <int RT>
 __global__ void __launch_bounds__(256) sh_rest_adam_views_kernel(const ShRestArgs a) {
     __shared__ __attribute__((aligned(16))) float s_out[256 / kWave][kWave * 15 * 3];
-    const uint32_t R = RT > 0 ? static_cast<uint32_t>(RT) : a.total_sh_rest;
-    const uint32_t lane = lane_id(), wv = threadIdx.x >> 6;
-    const uint32_t first = (blockIdx.x * 256u + wv * kWave);
-    if (first >= a.n) return;
-    sh_rest_block_to_lds<RT, true>(a, first, lane, s_out[wv]);
-    const uint32_t count = (a.n - first < kWave ? a.n - first : kWave) * R * 3u;
-    const size_t base = (size_t)first * R * 3u;
-    for (uint32_t e = 4u * lane; e < count; e += 4u * kWave) {
-        if (e + 4u <= count) {
-            float4 p4 = load_float4_nt(a.p + base + e), m4 = load_float4_nt(a.m + base + e), v4 = load_float4_nt(a.v + base + e);
-            const float4 g = *reinterpret_cast<const float4*>(&s_out[wv][e]);
-            adam_update(p4.x, m4.x, v4.x, g.x, a.h); adam_update(p4.y, m4.y, v4.y, g.y, a.h);
-            adam_update(p4.z, m4.z, v4.z, g.z, a.h); adam_update(p4.w, m4.w, v4.w, g.w, a.h);
-            store_float4_nt(a.p + base + e, p4); store_float4_nt(a.m + base + e, m4); store_float4_nt(a.v + base + e, v4);
+    const WaveBlock w = wave_block<RT>(a.n, a.total_sh_rest);
+    if (w.first >= a.n) return;
+    sh_rest_block_to_lds<true>(a, w, s_out[w.wv]);
+    float* const P = a.p + w.base; float* const M = a.m + w.base; float* const V = a.v + w.base;
+    for (uint32_t e = 4u * w.lane; e < w.count; e += 4u * kWave) {
+        if (e + 4u <= w.count) {
+            AdamPiece piece;
+            piece.load(P + e, M + e, V + e);
+            piece.step(P + e, M + e, V + e, *reinterpret_cast<const float4*>(&s_out[w.wv][e]), a.h);
         } else {
-            for (uint32_t j = e; j < count; ++j) {
-                float pp = a.p[base + j], mm = a.m[base + j], vv = a.v[base + j];
-                adam_update(pp, mm, vv, s_out[wv][j], a.h);
-                a.p[base + j] = pp; a.m[base + j] = mm; a.v[base + j] = vv;
-            }
+            adam_scalar_tail(P, M, V, e, w.count, a.h, [&](const uint32_t j) { return s_out[w.wv][j]; });
         }
     }
 }
@@ -740,12 +697,8 @@ __global__ void __launch_bounds__(256) sh_rest_backward_kernel(const ShRestArgs 
         const uint32_t e0 = 4u * v;
         const uint32_t p0 = e0 / 3u, c0 = e0 - 3u * p0;
         const bool full = e0 + 4u <= n_elems;
-        float4 p4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m4 = p4, v4 = p4;
-        if (FUSED && full) {                     // request the 48 bytes of state before the gradient is rebuilt
-            p4 = load_float4_nt(a.p + e0);                 // streamed once per step: non-temporal like the Adam kernel
-            m4 = load_float4_nt(a.m + e0);
-            v4 = load_float4_nt(a.v + e0);
-        }
+        float4 p4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m4 = p4, v4 = p4;           // hand-written piece: AdamPiece costs this kernel its register count (profiles/k12_k13_split.txt)
+        if (FUSED && full) { p4 = load_float4_nt(a.p + e0); m4 = load_float4_nt(a.m + e0); v4 = load_float4_nt(a.v + e0); }   // the 48 bytes of state are requested before the gradient is rebuilt (streamed once per step: non-temporal like the Adam kernel)
         const PairGrad q0 = pair_gradient<RT, false>(a, a.view[0], p0, n_pairs), q1 = pair_gradient<RT, false>(a, a.view[0], p0 + 1u, n_pairs);
         float g[4];
 #pragma unroll
@@ -757,25 +710,15 @@ __global__ void __launch_bounds__(256) sh_rest_backward_kernel(const ShRestArgs 
             const float qc0 = in_first ? q0.c[0] : q1.c[0], qc1 = in_first ? q0.c[1] : q1.c[1], qc2 = in_first ? q0.c[2] : q1.c[2];
             g[j] = qb * (c == 0u ? qc0 : (c == 1u ? qc1 : qc2));
         }
-        if (full) {
-            if (!FUSED) {
-                *reinterpret_cast<float4*>(a.grad_sh_rest + e0) = make_float4(g[0], g[1], g[2], g[3]);
-            } else {
-                adam_update(p4.x, m4.x, v4.x, g[0], a.h); adam_update(p4.y, m4.y, v4.y, g[1], a.h);
-                adam_update(p4.z, m4.z, v4.z, g[2], a.h); adam_update(p4.w, m4.w, v4.w, g[3], a.h);
-                store_float4_nt(a.p + e0, p4);
-                store_float4_nt(a.m + e0, m4);
-                store_float4_nt(a.v + e0, v4);
-            }
+        if (!FUSED) {
+            if (full) *reinterpret_cast<float4*>(a.grad_sh_rest + e0) = make_float4(g[0], g[1], g[2], g[3]);
+            else for (uint32_t j = 0; e0 + j < n_elems; ++j) a.grad_sh_rest[e0 + j] = g[j];
+        } else if (full) {
+            adam_update(p4.x, m4.x, v4.x, g[0], a.h); adam_update(p4.y, m4.y, v4.y, g[1], a.h);
+            adam_update(p4.z, m4.z, v4.z, g[2], a.h); adam_update(p4.w, m4.w, v4.w, g[3], a.h);
+            store_float4_nt(a.p + e0, p4); store_float4_nt(a.m + e0, m4); store_float4_nt(a.v + e0, v4);
         } else {
-            for (uint32_t j = 0; e0 + j < n_elems; ++j) {
-                if (!FUSED) a.grad_sh_rest[e0 + j] = g[j];
-                else {
-                    float pp = a.p[e0 + j], mm = a.m[e0 + j], vv = a.v[e0 + j];
-                    adam_update(pp, mm, vv, g[j], a.h);
-                    a.p[e0 + j] = pp; a.m[e0 + j] = mm; a.v[e0 + j] = vv;
-                }
-            }
+            adam_scalar_tail(a.p, a.m, a.v, e0, n_elems, a.h, [&](const uint32_t e) { return g[e - e0]; });
         }
     }
 }
@@ -786,181 +729,15 @@ hipError_t launch_sh_rest_backward(bool fused_adam, const ShRestArgs& a, hipStre
     if (n_elems >= (1ull << 32)) return hipErrorInvalidValue;        // 32-bit element indices: N * (K-1) * 3 < 2^32
     const uint64_t n_vec = (n_elems + 3) / 4;
     const unsigned blocks = static_cast<unsigned>(n_vec / 256 + 1 < 8192 ? n_vec / 256 + 1 : 8192);   // grid-stride: 32 workgroups per CU
-    const dim3 grid(blocks), block(256);
-    if (!fused_adam) {
-        if (a.total_sh_rest > 15) return hipErrorInvalidValue;
-        const dim3 ggrid((a.n + 255u) / 256u);
-        const bool views = a.view[0].slot != nullptr;           // sharded path: records + sum over views
-        if (a.total_sh_rest == 15) {
-            if (views) hipLaunchKernelGGL((sh_rest_gradient_kernel<15, true>), ggrid, block, 0, s, a);
-            else hipLaunchKernelGGL((sh_rest_gradient_kernel<15, false>), ggrid, block, 0, s, a);
-        } else {
-            if (views) hipLaunchKernelGGL((sh_rest_gradient_kernel<0, true>), ggrid, block, 0, s, a);
-            else hipLaunchKernelGGL((sh_rest_gradient_kernel<0, false>), ggrid, block, 0, s, a);
-        }
-    } else if (a.view[0].slot != nullptr) {                      // sharded path fused with Adam
-        if (a.total_sh_rest > 15) return hipErrorInvalidValue;
-        const dim3 ggrid((a.n + 255u) / 256u);
-        if (a.total_sh_rest == 15) hipLaunchKernelGGL(sh_rest_adam_views_kernel<15>, ggrid, block, 0, s, a);
-        else hipLaunchKernelGGL(sh_rest_adam_views_kernel<0>, ggrid, block, 0, s, a);
-    } else if (a.total_sh_rest == 15) {
-        hipLaunchKernelGGL((sh_rest_backward_kernel<true, 15>), grid, block, 0, s, a);
-    } else {
-        hipLaunchKernelGGL((sh_rest_backward_kernel<true, 0>), grid, block, 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-// ---- K13: Adam for all parameter groups in one launch (adam.cu:10-34), float4-vectorised, U pieces per thread ----------
-// g_adam_unroll = 1: 16-byte pieces per thread (fgs_debug_set_option(1, u)); measured on MI355X: 1, 2 and 4 are within 2 %
-// g_adam_reverse = 1 (fgs_debug_set_option(8, 0|1) in the dev build): reversed workgroup order (measured 0.837 vs 0.855 ms at S2, tools/ab_adam_order.py)
-// g_adam_nontemporal = 1 (fgs_debug_set_option(2, 0|1) in the dev build): non-temporal loads / stores (state is streamed once per step: +2.3 % measured)
-// (round 6, measured and withdrawn: the updated PARAMETERS alone as ordinary stores, on the idea that the next forward pass reads them first -- K1 0.227 vs 0.201 ms,
-// Adam 0.797 vs 0.782: dirty lines in eight L2s are the last thing the next kernel's reads want to meet, profiles/r06_ab_adam_param_nt.txt)
-
-template <bool NT> __device__ __forceinline__ float4 load4(const float* p) { return NT ? load_float4_nt(p) : *reinterpret_cast<const float4*>(p); }
-template <bool NT> __device__ __forceinline__ void store4(float* p, const float4 v) {
-    if (NT) store_float4_nt(p, v);
-    else *reinterpret_cast<float4*>(p) = v;
-}
-
-// Does the optimizer have to READ the gradient of block b (64 Gaussians) of this tensor? Flagged 0: every element is a zero the backward pass wrote --
-// skip the read (the kernel is HBM-bound; the index arithmetic is free).
-__device__ __forceinline__ bool adam_block_gradient_needed(const AdamArgs& a, const AdamGroup& G, const uint32_t b) {
-    if (a.live_blocks[b] != 0) return true;
-    // Belt and braces: the promise rests on the caller's proof that nobody touched the gradients since the backward pass,
-    // and a write that bypasses the framework's bookkeeping (`.grad.data.add_(...)`, a raw-pointer kernel) cannot be seen by
-    // it. One SENTINEL float per flagged-0 block and tensor (the first element of the block: the same cached 4 bytes for every
-    // float4 of the block) is read anyway; anything but +-0 there -- a whole-tensor edit such as hand-written weight decay,
-    // NaN / Inf -- and the block's gradients are read after all.
-    return !(G.grad[(size_t)b * 64u * G.row_len] == 0.0f);
-}
-
-// What to do with the elements first .. last (at most four consecutive floats of the [N, L] tensor)? They cover the rows first / L .. last / L, which lie in
-// at most two consecutive blocks of 64 Gaussians.
-//   kAdamRead : some block's gradient is needed -- the piece is read and stepped in full
-//   kAdamZero : no block's gradient is needed -- the piece is stepped with g = 0 without reading it
-//   kAdamSkip : as kAdamZero, and both blocks are QUIET (a.quiet_blocks: all moments of the block == 0.0f in every group of the launch). adam_update with
-//               g = m = v = 0 leaves m = v = +0 and p -= step_size * 0 / eps = p for eps > 0 and a finite step size (the host hands no quiet flags
-//               otherwise): the piece is neither loaded nor stored, and nothing is deferred -- memory is what the full piece would have left (+-0 aside)
-// A piece that needs a block's gradient clears that block's quiet byte, with a store only if it read a 1 (steady state: no stores).
-// Races between workgroups: skipping needs "gradient not needed", clearing needs "gradient needed", and within one tensor every piece of a block sees the
-// same live flag and the same sentinel -- so no piece of a tensor skips a block that another piece of that tensor steps on a gradient. Tensors can differ
-// only through their sentinels (one tensor edited behind the flags). A piece of an unedited tensor then reads the quiet byte as 1 or as the 0 another
-// tensor's piece just stored: it skips, or it runs kAdamZero on moments that are still all zero (its elements are written by nobody else) -- the identity
-// either way, bit for bit. A piece that runs across a block border writes +0 moments and the unchanged parameter into the quiet side: harmless, and the
-// reason quiet is defined by == 0.0f and not by the bit pattern.
-enum : int { kAdamSkip = 0, kAdamZero = 1, kAdamRead = 2 };
-__device__ __forceinline__ int adam_piece_plan(const AdamArgs& a, const AdamGroup& G, const int64_t first, const int64_t last) {
-    if (a.live_blocks == nullptr || G.row_len == 0u) return kAdamRead;
-    const uint32_t r0 = static_cast<uint32_t>(first) / G.row_len, r1 = static_cast<uint32_t>(last) / G.row_len;
-    const uint32_t b0 = r0 >> 6, b1 = r1 >> 6;
-    const bool need0 = adam_block_gradient_needed(a, G, b0), need1 = b1 == b0 ? need0 : adam_block_gradient_needed(a, G, b1);
-    if (a.quiet_blocks != nullptr) {
-        const uint8_t q0 = a.quiet_blocks[b0], q1 = b1 == b0 ? q0 : a.quiet_blocks[b1];
-        if (need0 && q0 != 0) a.quiet_blocks[b0] = 0;
-        if (b1 != b0 && need1 && q1 != 0) a.quiet_blocks[b1] = 0;
-        if (!need0 && !need1 && q0 != 0 && q1 != 0) return kAdamSkip;
-    }
-    return need0 || need1 ? kAdamRead : kAdamZero;
-}
-
-template <int U, bool NT>
-__global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
-    // a.reverse: workgroups walk the arenas from the end -- the gradient elements the backward pass wrote LAST are the ones most likely to
-    // still sit in the 256 MB memory-side cache
-    const uint32_t blk = a.reverse ? a.total_blocks - 1u - blockIdx.x : blockIdx.x;
-    int gidx = 0;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) if (j < a.n_groups && blk >= a.g[j].first_block) gidx = j;
-    const AdamGroup& G = a.g[gidx];
-    const int64_t block_base = (int64_t)(blk - G.first_block) * (256 * 4 * U);
-    float4 g4[U], p4[U], m4[U], v4[U];
-    bool full[U], run[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {                       // all loads of the thread are issued before any arithmetic
-        const int64_t base = block_base + ((int64_t)u * 256 + threadIdx.x) * 4;
-        full[u] = base + 4 <= G.n;
-        run[u] = false;
-        if (full[u]) {
-            const int plan = adam_piece_plan(a, G, base, base + 3);
-            run[u] = plan != kAdamSkip;
-            if (run[u]) {
-                g4[u] = plan == kAdamRead ? load4<NT>(G.grad + base) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                p4[u] = load4<NT>(G.param + base);
-                m4[u] = load4<NT>(G.exp_avg + base);
-                v4[u] = load4<NT>(G.exp_avg_sq + base);
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t base = block_base + ((int64_t)u * 256 + threadIdx.x) * 4;
-        if (full[u]) {
-            if (run[u]) {
-                adam_update(p4[u].x, m4[u].x, v4[u].x, g4[u].x, G.h); adam_update(p4[u].y, m4[u].y, v4[u].y, g4[u].y, G.h);
-                adam_update(p4[u].z, m4[u].z, v4[u].z, g4[u].z, G.h); adam_update(p4[u].w, m4[u].w, v4[u].w, g4[u].w, G.h);
-                store4<NT>(G.param + base, p4[u]);
-                store4<NT>(G.exp_avg + base, m4[u]);
-                store4<NT>(G.exp_avg_sq + base, v4[u]);
-            }
-        } else if (base < G.n) {
-            // the tensor's last (fewer than four) floats: the same plan, or a tensor of 4 k + 1 .. 3 floats would have its tail read and stepped whatever the flags say
-            const int plan = adam_piece_plan(a, G, base, G.n - 1);
-            for (int64_t e = base; plan != kAdamSkip && e < G.n; ++e) {
-                float pp = G.param[e], mm = G.exp_avg[e], vv = G.exp_avg_sq[e];
-                adam_update(pp, mm, vv, plan == kAdamRead ? G.grad[e] : 0.0f, G.h);
-                G.param[e] = pp; G.exp_avg[e] = mm; G.exp_avg_sq[e] = vv;
-            }
-        }
-    }
-}
-
-// ---- quiet scan: quiet_out[b] = "every moment of block b is zero", for a caller that cannot prove its flags current (once per invalidation, never per step) ----
-// One workgroup of 256 per block of 64 Gaussians: per group the block's 64 L floats of exp_avg and of exp_avg_sq are contiguous and start on a multiple of
-// 256 bytes behind the tensor's base -- 16-byte loads where the base is 16-byte aligned, scalar loads for the ragged block's tail and unaligned tensors.
-__global__ void __launch_bounds__(256) adam_quiet_scan_kernel(const AdamQuietScanArgs a) {
-    const uint32_t b = blockIdx.x;
-    const uint32_t rows = min(64u, a.rows - b * 64u);
-    bool zero = true;
-    for (int k = 0; k < a.n_groups; ++k) {
-        const size_t first = (size_t)b * 64u * a.row_len[k];
-        const uint32_t len = rows * a.row_len[k];
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            const float* t = (w == 0 ? a.m[k] : a.v[k]) + first;
-            const uint32_t vec = (reinterpret_cast<uintptr_t>(t) & 15u) == 0 ? len >> 2 : 0u;
-            for (uint32_t i = threadIdx.x; i < vec; i += 256u) {
-                const float4 x = load_float4_nt(t + 4u * i);
-                zero = zero && x.x == 0.0f && x.y == 0.0f && x.z == 0.0f && x.w == 0.0f;
-            }
-            for (uint32_t e = 4u * vec + threadIdx.x; e < len; e += 256u) zero = zero && t[e] == 0.0f;
-        }
-    }
-    const int all_zero = __syncthreads_and(zero ? 1 : 0);
-    if (threadIdx.x == 0) a.quiet_out[b] = all_zero ? 1 : 0;
-}
-
-hipError_t launch_adam_quiet_scan(const AdamQuietScanArgs& a, hipStream_t s) {
-    if (a.rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(adam_quiet_scan_kernel, dim3((a.rows + 63u) / 64u), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_adam(const AdamArgs& a_in, hipStream_t s) {
-    AdamArgs a = a_in;
-    const int unroll_opt = g_adam_unroll, nontemporal = g_adam_nontemporal;
-    const int u = nontemporal ? 1 : (unroll_opt == 2 || unroll_opt == 4 ? unroll_opt : 1);
-    uint32_t blocks = 0;                                  // first_block / total_blocks depend on the elements per workgroup
-    for (int k = 0; k < a.n_groups; ++k) { a.g[k].first_block = blocks; blocks += static_cast<uint32_t>((a.g[k].n + 1024 * u - 1) / (1024 * u)); }
-    a.total_blocks = blocks;
-    a.reverse = g_adam_reverse;
-    if (blocks == 0) return hipSuccess;
-    if (nontemporal) hipLaunchKernelGGL((adam_kernel<1, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (u == 1) hipLaunchKernelGGL((adam_kernel<1, false>), dim3(blocks), dim3(256), 0, s, a);
-    else if (u == 2) hipLaunchKernelGGL((adam_kernel<2, false>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((adam_kernel<4, false>), dim3(blocks), dim3(256), 0, s, a);
-    return hipGetLastError();
+    const dim3 grid(blocks), ggrid((a.n + 255u) / 256u), block(256);       // flat kernel; a wave per 64 Gaussians
+    const bool views = a.view[0].slot != nullptr;                          // sharded path: records + sum over views
+    return dispatch_sh_rest(a.total_sh_rest, [&](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        if (!fused_adam && views) hipLaunchKernelGGL((sh_rest_gradient_kernel<RT, true>), ggrid, block, 0, s, a);
+        else if (!fused_adam) hipLaunchKernelGGL((sh_rest_gradient_kernel<RT, false>), ggrid, block, 0, s, a);
+        else if (views) hipLaunchKernelGGL(sh_rest_adam_views_kernel<RT>, ggrid, block, 0, s, a);
+        else hipLaunchKernelGGL((sh_rest_backward_kernel<true, RT>), grid, block, 0, s, a);
+    });
 }
 
 }  // namespace fgs

@@ -686,3 +686,47 @@ def check_records_against_f64(be, oracle, params, view, K=16, aa=False, device='
         for th, (n_dev, n_o32) in counts.items():
             assert n_dev <= 1.25 * n_o32 + 4.0 * max(n_o32, 1) ** 0.5 + 2, (label, name, f'entries farther than {th:g} from the fp64 value', report)
     return report
+
+
+def fused_equals_backward_then_adam(be, params, view, K=16, aa=False, unaligned=False, device='cpu', same=torch.equal, moments=None):
+    """fused == backward -> FusedAdam.step() for all six groups, including invisible Gaussians, bit for bit in the simulator.
+    `unaligned`: the fused side's parameters and moments start 4 bytes past a 16-byte boundary (the fused kernel's scalar path).
+    `device`, `same`: tests/k12_fold_cases.py runs this on hardware too, where K11's float atomics allow no bit-for-bit comparison: `same` is then
+    a relative bar, which is why the parameters are compared as steps from their start as well (implied by the first comparison when it is exact),
+    and `moments` are seeded_moments, whose second moment has a floor (that docstring says why)."""
+    n = params['means'].shape[0]
+    params = {k: v.to(device) for k, v in params.items()}
+    S, RS = settings_pair(view, K, aa, device=device)
+    order = ('means', 'sh_coefficients_0', 'sh_coefficients_rest', 'opacities', 'scales', 'rotations')
+    lrs = [1.6e-4, 2.5e-3, 1.25e-4, 2.5e-2, 5e-3, 1e-3]
+    ref_p = {k: params[k].clone() for k in order}
+    ref_m = {k: torch.randn_like(params[k]) * 1e-3 for k in order}
+    ref_v = {k: torch.rand_like(params[k]) * 1e-6 for k in order}
+    if moments is not None:                                              # (exp_avg, exp_avg_sq) of group i, e.g. seeded_moments
+        for i, k in enumerate(order):
+            ref_m[k], ref_v[k] = (t.to(device) for t in moments(params[k].shape, 5 + i))
+    fus_p, fus_m, fus_v = ({k: d[k].clone() for k in order} for d in (ref_p, ref_m, ref_v))
+    if unaligned:
+        def odd(t):
+            base = torch.empty(t.numel() + 8, dtype=t.dtype, device=device)
+            shift = (1 - base.data_ptr() // 4) % 4                      # first float whose address is 4 bytes past a 16-byte boundary
+            o = base[shift:shift + t.numel()].view(t.shape); o.copy_(t)
+            assert t.numel() == 0 or o.data_ptr() % 16 == 4
+            return o
+        fus_p, fus_m, fus_v = ({k: odd(d[k]) for k in order} for d in (fus_p, fus_m, fus_v))
+    gi = torch.randn(3, view.height, view.width, generator=torch.Generator().manual_seed(2)).to(device)
+    dens_ref, dens_fus = torch.zeros(2, n, device=device), torch.zeros(2, n, device=device)
+    for step in (1, 2):
+        res = be.forward(*[ref_p[k] for k in NAMES], RS)
+        grads = be.backward(dens_ref, gi, res.image, ref_p['means'], ref_p['scales'], ref_p['rotations'], ref_p['opacities'],
+                                     ref_p['sh_coefficients_rest'], res.buffers, RS, res.state)
+        gmap = dict(zip(NAMES, grads))
+        be.adam_step_multi([gmap[k] for k in order], [ref_p[k] for k in order], [ref_m[k] for k in order],
+                                    [ref_v[k] for k in order], [step] * 6, lrs, 0.9, 0.999, 1e-15)
+        res2 = be.forward(*[fus_p[k] for k in NAMES], RS)
+        be.backward_adam_fused(dens_fus, gi, res2.image, [fus_p[k] for k in order], [fus_m[k] for k in order],
+                                        [fus_v[k] for k in order], res2.buffers, RS, res2.state, step, lrs)
+        for k in order:
+            assert same(fus_p[k], ref_p[k]) and same(fus_p[k] - params[k], ref_p[k] - params[k]), (step, k)
+            assert same(fus_m[k], ref_m[k]) and same(fus_v[k], ref_v[k]), (step, k)
+    assert same(dens_ref, dens_fus)

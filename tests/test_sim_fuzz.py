@@ -7,7 +7,7 @@ import os
 import pytest
 
 import helpers
-from test_sim_parity import _run, fused_equals_backward_then_adam
+from test_sim_parity import _run
 
 
 _SEEDS = range(*(int(x) for x in os.environ['FGS_FUZZ_SEEDS'].split('-'))) if os.environ.get('FGS_FUZZ_SEEDS') else range(32)
@@ -23,4 +23,4 @@ def test_random_configuration_in_the_simulator(sim_backend, oracle, seed):
 def test_random_configuration_fused_equals_unfused_in_the_simulator(sim_backend, seed):
     """The same configurations: fgs_backward_adam_fused == fgs_backward -> fgs_adam_step_multi, two steps, bit for bit."""
     p, view, K, aa, label = helpers.fuzz_configuration(seed)
-    fused_equals_backward_then_adam(helpers.poisoned(sim_backend), p, view, K, aa)
+    helpers.fused_equals_backward_then_adam(helpers.poisoned(sim_backend), p, view, K, aa)

@@ -94,7 +94,7 @@ def test_product_flavour_of_the_sources(sim_product_backend, sim_backend, oracle
     assert torch.equal(res.image, dev.image) and res.state == dev.state
     small, view_s = make_s0(n=400)
     small['means'][:40, 2] = -10.0
-    fused_equals_backward_then_adam(sim_product_backend, small, view_s)
+    helpers.fused_equals_backward_then_adam(sim_product_backend, small, view_s)
     test_adam_single_and_multi(sim_product_backend, oracle)
     test_forward_without_host_synchronisation(sim_product_backend, oracle)
 
@@ -265,48 +265,11 @@ def test_adam_single_and_multi(sim_backend, oracle):
     assert np.array_equal(tp[4].numpy(), P[4])
 
 
-def fused_equals_backward_then_adam(sim_backend, params, view, K=16, aa=False, unaligned=False):
-    """fused == backward -> FusedAdam.step() for all six groups, including invisible Gaussians, bit for bit in the simulator.
-    `unaligned`: the fused side's parameters and moments start 4 bytes past a 16-byte boundary (the fused kernel's scalar path)."""
-    n = params['means'].shape[0]
-    S, RS = helpers.settings_pair(view, K, aa)
-    order = ('means', 'sh_coefficients_0', 'sh_coefficients_rest', 'opacities', 'scales', 'rotations')
-    lrs = [1.6e-4, 2.5e-3, 1.25e-4, 2.5e-2, 5e-3, 1e-3]
-    ref_p = {k: params[k].clone() for k in order}
-    ref_m = {k: torch.randn_like(params[k]) * 1e-3 for k in order}
-    ref_v = {k: torch.rand_like(params[k]) * 1e-6 for k in order}
-    fus_p, fus_m, fus_v = ({k: d[k].clone() for k in order} for d in (ref_p, ref_m, ref_v))
-    if unaligned:
-        def odd(t):
-            base = torch.empty(t.numel() + 8, dtype=t.dtype)
-            shift = (1 - base.data_ptr() // 4) % 4                      # first float whose address is 4 bytes past a 16-byte boundary
-            o = base[shift:shift + t.numel()].view(t.shape); o.copy_(t)
-            assert o.data_ptr() % 16 == 4
-            return o
-        fus_p, fus_m, fus_v = ({k: odd(d[k]) for k in order} for d in (fus_p, fus_m, fus_v))
-    gi = torch.randn(3, view.height, view.width, generator=torch.Generator().manual_seed(2))
-    dens_ref, dens_fus = torch.zeros(2, n), torch.zeros(2, n)
-    for step in (1, 2):
-        res = sim_backend.forward(*[ref_p[k] for k in helpers.NAMES], RS)
-        grads = sim_backend.backward(dens_ref, gi, res.image, ref_p['means'], ref_p['scales'], ref_p['rotations'], ref_p['opacities'],
-                                     ref_p['sh_coefficients_rest'], res.buffers, RS, res.state)
-        gmap = dict(zip(helpers.NAMES, grads))
-        sim_backend.adam_step_multi([gmap[k] for k in order], [ref_p[k] for k in order], [ref_m[k] for k in order],
-                                    [ref_v[k] for k in order], [step] * 6, lrs, 0.9, 0.999, 1e-15)
-        res2 = sim_backend.forward(*[fus_p[k] for k in helpers.NAMES], RS)
-        sim_backend.backward_adam_fused(dens_fus, gi, res2.image, [fus_p[k] for k in order], [fus_m[k] for k in order],
-                                        [fus_v[k] for k in order], res2.buffers, RS, res2.state, step, lrs)
-        for k in order:
-            assert torch.equal(fus_p[k], ref_p[k]), (step, k)
-            assert torch.equal(fus_m[k], ref_m[k]) and torch.equal(fus_v[k], ref_v[k]), (step, k)
-    assert torch.equal(dens_ref, dens_fus)
-
-
 @pytest.mark.parametrize('K,unaligned', [(16, False), (4, False), (16, True)])
 def test_fused_backward_adam_equals_backward_then_adam(sim_backend, oracle, K, unaligned):
     params, view = make_s0(n=400)
     params['means'][:40, 2] = -10.0                      # some invisible Gaussians: zero grad, moments still decay
-    fused_equals_backward_then_adam(sim_backend, params, view, K, False, unaligned)
+    helpers.fused_equals_backward_then_adam(sim_backend, params, view, K, False, unaligned)
 
 
 @pytest.mark.parametrize('n,w,h,focal', [(20_000, 320, 180, 237.0), (60_001, 640, 360, 473.0)])

@@ -8,7 +8,7 @@ make -s -j8 >/dev/null
 extra=""
 case $src in
   preprocess.hip) extra="-ffp-contract=off -Xclang -target-feature -Xclang -packed-fp32-ops";;
-  binning.hip|preprocess_backward.hip|aux_ops.hip|densify.hip) extra="-ffp-contract=off";;
+  binning.hip|preprocess_backward.hip|adam.hip|aux_ops.hip|densify.hip) extra="-ffp-contract=off";;
   blend_backward.hip|blend_forward.hip|loss.hip|radix_sort.hip) extra="-Xclang -target-feature -Xclang -packed-fp32-ops";;
 esac
 obj=/tmp/fgs_variant_${name}_${src%.hip}.o
