@@ -76,7 +76,7 @@ constexpr unsigned kColumnsTopDown = 252u, kColumnsBottomUp = 251u;   // one ver
 constexpr unsigned kBandsThroughPlan = 253u;         // A/B only: the round-1 bands, but with the plan's dependent load on every workgroup's path
 FGS_SWITCH(g_tile_row_group, static_cast<int>(kColumnsTopDown));   // blend_forward.hip: tile -> workgroup mapping (254: device-side block plan; 0: round-1 bands; 1..64 row groups)
 #ifdef FGS_DEV_SWITCHES
-FGS_SWITCH(g_k11_chain_waves, 4096);                 // blend_backward.hip, option 14: waves of the chained K11 exhibit (variant 5); 4096 = 16 resident waves x 256 CUs
+FGS_SWITCH(g_k11_chain_waves, 4096);                 // blend_backward_exhibits.hip, option 14: waves of the chained K11 exhibit (variant 5); 4096 = 16 resident waves x 256 CUs
 #endif
 FGS_SWITCH(g_seq_tiles, kSeqTiles);                  // preprocess.hip, option 5: PreprocessArgs::seq_tiles of every K1 launch
 FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
@@ -297,8 +297,10 @@ FGS_SWITCH(g_adam_nontemporal, 1);                                           // 
 FGS_SWITCH(g_adam_unroll, 1);                                                // option 1: 1, 2 or 4 float4 pieces per thread
 #ifdef FGS_DEV_SWITCHES
 extern std::atomic<int> g_backward_ablate;
-extern std::atomic<int> g_k11m_max_blocks;
-extern std::atomic<int> g_backward_variant;                                  // 3 compact (default), 0 / 2 systolic, 1 strip, 4 lane = pixel (blend_backward.hip)
+extern std::atomic<int> g_k11m_max_blocks;                                   // blend_backward_exhibits.hip
+extern std::atomic<int> g_backward_variant;                                  // 3 compact (default, blend_backward.hip); 0 / 2 systolic, 1 strip, 4 lane = pixel, 5 chained (blend_backward_exhibits.hip)
+// the exhibit kernel of a.variant != 3 alone (blend_backward_exhibits.hip); launch_blend_backward adds the fold / dirty-mark kernel behind it and reads the error
+void launch_blend_backward_exhibit(const BlendBackwardArgs& a, hipStream_t s);
 #endif
 int blend_backward_variant();                                                // the K11 formulation of this pass (always 3 in the product build)
 hipError_t launch_wave_selftest(uint32_t* out /*[4*64]*/, hipStream_t s);

@@ -403,7 +403,8 @@ int32_t fgs_debug_depth_sort(uint32_t* keys0, uint32_t* keys1, uint32_t* vals0, 
                              void* temp, size_t temp_bytes, void* stream);
 /* ---- libfgs_hip_dev.so only (built with -DFGS_DEV_SWITCHES: `make -C faster-gaussian-splatting_amd/csrc dev`). The product library has ONE formulation
  * of every kernel and no process-wide switches (every switch below is a compile-time constant there, csrc/fgs_kernels.h: FGS_SWITCH); the A/B tools
- * under tools/ and the variant tests load the dev library. ---- */
+ * under tools/ and the variant tests load the dev library. The K11 formulations other than 3 are kernels of csrc/blend_backward_exhibits.hip,
+ * a unit that only the dev library is built from. ---- */
 #ifdef FGS_DEV_SWITCHES
 /* Selects the blend-backward formulation: 3 (default) = live-bucket list + compacted pixels + two-value pipeline state, 2 / 0 =
  * round-1 systolic form (dL/dC from global memory / LDS), 1 = strip (lane = pixel, DPP reductions), 4 = lane = pixel walk with the

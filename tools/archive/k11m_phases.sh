@@ -1,6 +1,7 @@
 #!/bin/bash
 # Where does a wave of K11's lane = pixel variant spend its cycles? Separate library with cycle-counter probes between the phases
-# (-DFGS_K11M_PHASES, csrc/blend_backward.hip; the product library is untouched).
+# (-DFGS_K11M_PHASES; the product library is untouched).
+# STALE: variant 4 and this probe live in csrc/blend_backward_exhibits.hip (dev library only) -- see tools/README.md.
 # usage: bash tools/k11m_phases.sh build   (here)      bash tools/k11m_phases.sh run   (on the GPU box)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}; C=$R/faster-gaussian-splatting_amd/csrc; LIB=$R/faster-gaussian-splatting_amd/libfgs_hip_k11mphases.so
