@@ -3,6 +3,8 @@
 One `Backend` wraps one loaded library handle. The product uses `default_backend()` (libfgs_hip.so); the test-suite also
 builds one around the CPU simulation library to exercise this exact code path without a GPU.
 Mirrors what the reference does in C++ in rasterization_api.cu:13-247 and utils/torch_utils.h:6-12.
+
+A check that several entries make is one function below; where the entries differ in what they check it takes a flag (tests/glue_cases.py).
 """
 from __future__ import annotations
 
@@ -48,6 +50,10 @@ class ForwardAuxResult(NamedTuple):
     state: tuple
 
 
+PARAMETER_NAMES = ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest')
+BACKWARD_PARAMETER_NAMES = PARAMETER_NAMES[:4] + PARAMETER_NAMES[5:]      # the backward passes do not read sh_coefficients_0
+
+
 def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None or t.numel() == 0 else t.data_ptr()
 
@@ -63,9 +69,72 @@ def _stream_of(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def total_sh_rest(sh_rest: torch.Tensor) -> int:
+    """Rest coefficients per channel of a [N, total_rest, 3] tensor; 0 for an (empty) tensor of any other rank."""
+    return sh_rest.shape[1] if sh_rest.dim() == 3 else 0
+
+
+def gradient_shapes(n: int, total_rest: int) -> tuple:
+    """Shapes of the six gradients in the order every backward pass writes them: means, scales, rotations, opacities, sh0, sh_rest."""
+    return ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3))
+
+
+def _state_tuple(st: _lib.ForwardState) -> tuple:
+    return (st.n_visible, st.n_instances, st.n_buckets, st.selector)
+
+
+def _pointer_array(tensors: Sequence[torch.Tensor], k: int):
+    return (C.c_void_p * k)(*[_ptr(t) for t in tensors])
+
+
+def _shard_counts(shard_counts: Sequence[int] | None) -> tuple:
+    """(int32 array or None, its length) of the optional records-per-shard list of the two record entries."""
+    k = len(shard_counts) if shard_counts else 0
+    return ((C.c_int32 * k)(*[int(c) for c in shard_counts]) if k else None), k
+
+
+def _empty_bytes(nbytes: int, device: torch.device) -> torch.Tensor:
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _check_block_flags(name: str, flags: Optional[torch.Tensor], n: int, device: torch.device, owner: str = 'parameters') -> None:
+    if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
+        raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the {owner}\' device')
+
+
+def _gradients_out(out, shapes: tuple, device: torch.device, shapes_only: bool = False) -> tuple:
+    """The six gradient tensors of a backward pass: fresh ones, or the caller's `out` after a check. shapes_only: the sharded owner pass, whose
+    parameter check has looked at dtype, strides and device of `out` already."""
+    if out is None:
+        return tuple(torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes)
+    for g, sh in zip(out, shapes):
+        if tuple(g.shape) != sh or not (shapes_only or (g.dtype == torch.float32 and g.is_contiguous() and g.device == device)):
+            raise RuntimeError(f'preallocated gradient has shape {tuple(g.shape)}, expected {"" if shapes_only else "contiguous float32 "}{sh}')
+    return tuple(out)
+
+
+def _densification(densification_info, n: int, device: torch.device, validate: bool):
+    """None and an empty tensor both mean "no statistics" (api:136). validate: the plain backward passes; the fused and sharded ones take it as it comes."""
+    dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
+    if validate and dens is not None and (dens.dtype != torch.float32 or not dens.is_contiguous() or dens.device != device or dens.numel() != 2 * n):
+        raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
+    return dens
+
+
+def _check_acc_records(acc_records: torch.Tensor, n_visible: Sequence[int], k: int, device: torch.device) -> int:
+    """sum(n_visible), once the accumulator records of the `k` views have been checked against it."""
+    total = int(sum(n_visible))
+    if len(n_visible) != k or (total > 0 and (acc_records.dtype != torch.float32 or acc_records.numel() < 9 * total
+                                              or not acc_records.is_contiguous() or acc_records.device != device)):
+        raise RuntimeError('acc_records must be contiguous float32 [sum(n_visible), 9] and n_visible one entry per view')
+    return total
+
+
 class Backend:
     def __init__(self, lib: C.CDLL):
         self.lib = lib
+        self._pending_counts: list = []          # (pinned host tensor, event) of the count read-backs still in flight (forward_counts)
+        self._relocation_table: dict = {}        # device -> the 2500-entry table of relocation_adjustment
 
     # -- helpers ---------------------------------------------------------------------------------------------------
     def _check(self, status: int, what: str) -> None:
@@ -104,18 +173,26 @@ class Backend:
                 return 0
         return buffers, _lib.RESIZE_FN(resize)
 
+    def _forward_state(self, settings: RasterizerSettings, total_rest: int, device: torch.device) -> tuple:
+        """(Settings, the tensors it points into, the four resizable buffers, their callback, an empty ForwardState): the caller keeps all of it
+        referenced until the library call has returned."""
+        keep: list = []
+        S = self._settings(settings, total_rest, device, keep)
+        buffers, cb = self._make_resizer(device, 4)
+        return S, keep, buffers, cb, _lib.ForwardState()
+
+    def _forward_setup(self, params: Sequence[torch.Tensor], settings: RasterizerSettings) -> tuple:
+        """Checks the six parameter tensors: (their device, *_forward_state)."""
+        device = self._check_params(params, PARAMETER_NAMES)
+        return (device, *self._forward_state(settings, total_sh_rest(params[5]), device))
+
     # -- entry points -----------------------------------------------------------------------------------------------
     def forward(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings,
                 instance_capacity: int | None = None) -> ForwardResult:
         """instance_capacity: None = fgs_forward (one host read of the counts); an int = fgs_forward_async, no host wait -- state then
         holds bounds (N, capacity, ...) and `forward_counts` tells later whether the capacity was enough."""
-        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
-        keep: list = []
-        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        device, S, keep, buffers, cb, st = self._forward_setup((means, scales, rotations, opacities, sh0, sh_rest), settings)
         image = torch.empty((3, settings.height, settings.width), dtype=torch.float32, device=device)
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
         if instance_capacity is None:
             self._check(self.lib.fgs_forward(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
                                              means.shape[0], C.byref(S), image.data_ptr(), cb, None, C.byref(st), _stream_of(device)),
@@ -124,7 +201,7 @@ class Backend:
             self._check(self.lib.fgs_forward_async(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
                                                    means.shape[0], C.byref(S), image.data_ptr(), int(instance_capacity), cb, None, C.byref(st),
                                                    _stream_of(device)), 'fgs_forward_async')
-        return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
+        return ForwardResult(image, tuple(buffers), _state_tuple(st))
 
     def forward_aux(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings, alpha: bool = True,
                     depth: bool = True, instance_capacity: int | None = None) -> ForwardAuxResult:
@@ -134,18 +211,13 @@ class Backend:
             raise RuntimeError('forward_aux: the asynchronous forward pass (instance_capacity) does not return maps; use forward() or drop the capacity')
         if not (alpha or depth):
             raise RuntimeError('forward_aux: neither alpha nor depth requested (use forward)')
-        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
-        keep: list = []
-        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        device, S, keep, buffers, cb, st = self._forward_setup((means, scales, rotations, opacities, sh0, sh_rest), settings)
         image = torch.empty((3, settings.height, settings.width), dtype=torch.float32, device=device)
         maps = [torch.empty((settings.height, settings.width), dtype=torch.float32, device=device) if wanted else None for wanted in (alpha, depth)]
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
         self._check(self.lib.fgs_forward_aux(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
                                              means.shape[0], C.byref(S), image.data_ptr(), *[m.data_ptr() if m is not None else None for m in maps],
                                              cb, None, C.byref(st), _stream_of(device)), 'fgs_forward_aux')
-        return ForwardAuxResult(image, maps[0], maps[1], tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
+        return ForwardAuxResult(image, maps[0], maps[1], tuple(buffers), _state_tuple(st))
 
     def forward_counts(self, result: ForwardResult, n_primitives: int):
         """Enqueues the read-back of (n_visible, n_instances, capacity_exceeded) of a forward pass; returns (pinned int32[3] tensor, event).
@@ -160,44 +232,33 @@ class Backend:
             # The copy is a raw hipMemcpyAsync that torch's caching host allocator knows nothing about: if the caller drops `host` before the
             # copy has run (forward under no_grad, an exception, a freed graph), the pinned block would go back to the cache and the late copy
             # would land in whoever got it next. Keep every buffer referenced here until its event has completed.
-            pending = self.__dict__.setdefault('_pending_counts', [])
-            pending[:] = [(h, e) for h, e in pending if not e.query()]
-            pending.append((host, event))
+            self._pending_counts[:] = [(h, e) for h, e in self._pending_counts if not e.query()]
+            self._pending_counts.append((host, event))
         return host, event
 
     def inference(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings, to_chw: bool,
                   clamp_output: bool, return_state: bool = False):
-        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
-        keep: list = []
-        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        device, S, keep, buffers, cb, st = self._forward_setup((means, scales, rotations, opacities, sh0, sh_rest), settings)
         shape = (3, settings.height, settings.width) if to_chw else (settings.height, settings.width, 3)
         image = torch.empty(shape, dtype=torch.float32, device=device)
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
         self._check(self.lib.fgs_inference(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
                                            means.shape[0], C.byref(S), image.data_ptr(), int(to_chw), int(clamp_output), cb, None,
                                            C.byref(st), _stream_of(device)), 'fgs_inference')
         if return_state:
-            return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
+            return ForwardResult(image, tuple(buffers), _state_tuple(st))
         return image
 
     def inference_aux(self, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings, to_chw: bool,
                       clamp_output: bool, alpha: bool = True, depth_expected: bool = True, depth_median: bool = True) -> dict:
         """fgs_inference_aux: the forward-only render plus the requested per-pixel maps of the same walk, float32 [H,W] (include/fgs_hip.h).
         Returns {'rgb', 'alpha'?, 'depth'?, 'depth_median'?}; 'rgb' is bit-identical to `inference`."""
-        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
-        keep: list = []
-        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        device, S, keep, buffers, cb, st = self._forward_setup((means, scales, rotations, opacities, sh0, sh_rest), settings)
         shape = (3, settings.height, settings.width) if to_chw else (settings.height, settings.width, 3)
         out = {'rgb': torch.empty(shape, dtype=torch.float32, device=device)}
         for name, wanted in (('alpha', alpha), ('depth', depth_expected), ('depth_median', depth_median)):
             if wanted:
                 out[name] = torch.empty((settings.height, settings.width), dtype=torch.float32, device=device)
         maps = [out[k].data_ptr() if k in out else None for k in ('alpha', 'depth', 'depth_median')]
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
         self._check(self.lib.fgs_inference_aux(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest),
                                                means.shape[0], C.byref(S), out['rgb'].data_ptr(), int(to_chw), int(clamp_output), *maps, cb, None,
                                                C.byref(st), _stream_of(device)), 'fgs_inference_aux')
@@ -205,21 +266,19 @@ class Backend:
 
     def pruning_scores(self, scores, means, scales, rotations, opacities, sh0, sh_rest, settings: RasterizerSettings) -> None:
         """Accumulates the Speedy-Splat importance scores of one view into `scores` [N] (rasterization.py:159-178)."""
-        device = self._check_params((scores, means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('scores', 'means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
+        device = self._check_params((scores, means, scales, rotations, opacities, sh0, sh_rest), ('scores',) + PARAMETER_NAMES)
         if scores.numel() != means.shape[0]:
             raise RuntimeError('scores must have one entry per Gaussian')
-        keep: list = []
-        S = self._settings(settings, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
+        S, keep, buffers, cb, st = self._forward_state(settings, total_sh_rest(sh_rest), device)
         self._check(self.lib.fgs_pruning_scores(_ptr(scores), _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0),
                                                 _ptr(sh_rest), means.shape[0], C.byref(S), cb, None, C.byref(st), _stream_of(device)),
                     'fgs_pruning_scores')
 
     def _scratch(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
-        nbytes = int(self.lib.fgs_backward_scratch_bytes(n, int(settings.width), int(settings.height)))
-        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+        return _empty_bytes(self.lib.fgs_backward_scratch_bytes(n, int(settings.width), int(settings.height)), device)
+
+    def _scratch_aux(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
+        return _empty_bytes(self.lib.fgs_backward_aux_scratch_bytes(n, int(settings.width), int(settings.height)), device)
 
     def backward(self, densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings,
                  state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
@@ -228,86 +287,45 @@ class Backend:
         `live_blocks`, `reached_blocks`: optional uint8 [ceil(N / 64)] on the device, filled with 1 / 0 per block of 64 Gaussians: some Gaussian of the
         block is visible / was reached by the backward blend pass. 0 = every gradient of the block is zero (still written) -- what
         adam_step_multi(live_blocks=...) needs to skip reading those zeros; `reached_blocks` flags a superset of the zero blocks."""
-        device = self._check_params((means, scales, rotations, opacities, sh_rest), ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest'))
-        keep: list = []
-        n = means.shape[0]
-        total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
-        S = self._settings(settings, total_rest, device, keep)
-        grad_image = grad_image.to(dtype=torch.float32).contiguous()
-        shapes = ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3))
-        if out is None:
-            grads = tuple(torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes)
-        else:
-            grads = tuple(out)
-            for g, sh in zip(grads, shapes):
-                if tuple(g.shape) != sh or g.dtype != torch.float32 or not g.is_contiguous() or g.device != device:
-                    raise RuntimeError(f'preallocated gradient has shape {tuple(g.shape)}, expected contiguous float32 {sh}')
-        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None   # api:136
-        if dens is not None and (dens.dtype != torch.float32 or not dens.is_contiguous() or dens.device != device or dens.numel() != 2 * n):
-            raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
-        scratch = self._scratch(n, settings, device)
-        st = _lib.ForwardState(*state)
-        for name, flags in (('live_blocks', live_blocks), ('reached_blocks', reached_blocks)):
-            if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
-                raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
-        self._check(self.lib.fgs_backward_reached(_ptr(grad_image), _ptr(image), None, None, None, _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities),
-                                                  _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]),
-                                                  _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
-                                                  _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
-                                                  _stream_of(device)),
-                    'fgs_backward')
-        return grads
+        return self.backward_aux(densification_info, grad_image, None, None, image, None, means, scales, rotations, opacities, sh_rest, buffers, settings,
+                                 state, out, live_blocks, reached_blocks)
 
     def backward_aux(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
                      buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
                      reached_blocks: Optional[torch.Tensor] = None) -> tuple:
-        """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero; both None is `backward`
-        exactly). `depth` is the expected-depth map the forward pass returned (needed with grad_depth)."""
-        if grad_alpha is None and grad_depth is None:
-            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state, out, live_blocks,
-                                 reached_blocks)
-        device = self._check_params((means, scales, rotations, opacities, sh_rest), ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest'))
+        """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero). `depth` is the expected-depth
+        map the forward pass returned (needed with grad_depth). Both None is `backward` exactly: no map is looked at, the scratch is `_scratch`'s and
+        errors name fgs_backward; with a map gradient the scratch is `_scratch_aux`'s and errors name fgs_backward_aux."""
+        aux = grad_alpha is not None or grad_depth is not None
+        device = self._check_params((means, scales, rotations, opacities, sh_rest), BACKWARD_PARAMETER_NAMES)
         keep: list = []
         n = means.shape[0]
-        total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
+        total_rest = total_sh_rest(sh_rest)
         S = self._settings(settings, total_rest, device, keep)
-        hw = (int(settings.height), int(settings.width))
         grad_image = grad_image.to(dtype=torch.float32).contiguous()
-        for name, t in (('grad_alpha', grad_alpha), ('grad_depth', grad_depth), ('depth', depth if grad_depth is not None else None)):
-            if t is not None and (tuple(t.shape) != hw or t.device != device):
-                raise RuntimeError(f'{name} must be a [H,W] = {hw} tensor on the parameters\' device')
-        if grad_depth is not None and depth is None:
-            raise RuntimeError('backward_aux: grad_depth needs the expected-depth map of forward_aux')
-        grad_alpha = grad_alpha.to(dtype=torch.float32).contiguous() if grad_alpha is not None else None
-        grad_depth = grad_depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
+        if aux:
+            hw = (int(settings.height), int(settings.width))
+            for name, t in (('grad_alpha', grad_alpha), ('grad_depth', grad_depth), ('depth', depth if grad_depth is not None else None)):
+                if t is not None and (tuple(t.shape) != hw or t.device != device):
+                    raise RuntimeError(f'{name} must be a [H,W] = {hw} tensor on the parameters\' device')
+            if grad_depth is not None and depth is None:
+                raise RuntimeError('backward_aux: grad_depth needs the expected-depth map of forward_aux')
+            grad_alpha = grad_alpha.to(dtype=torch.float32).contiguous() if grad_alpha is not None else None
+            grad_depth = grad_depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
         depth = depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
-        shapes = ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3))
-        if out is None:
-            grads = tuple(torch.empty(sh, dtype=torch.float32, device=device) for sh in shapes)
-        else:
-            grads = tuple(out)
-            for g, sh in zip(grads, shapes):
-                if tuple(g.shape) != sh or g.dtype != torch.float32 or not g.is_contiguous() or g.device != device:
-                    raise RuntimeError(f'preallocated gradient has shape {tuple(g.shape)}, expected contiguous float32 {sh}')
-        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
-        if dens is not None and (dens.dtype != torch.float32 or not dens.is_contiguous() or dens.device != device or dens.numel() != 2 * n):
-            raise RuntimeError('densification_info must be a contiguous float32 [2, N] tensor on the parameters\' device')
-        for name, flags in (('live_blocks', live_blocks), ('reached_blocks', reached_blocks)):
-            if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
-                raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
-        scratch = self._scratch_aux(n, settings, device)
+        grads = _gradients_out(out, gradient_shapes(n, total_rest), device)
+        dens = _densification(densification_info, n, device, validate=True)
+        _check_block_flags('live_blocks', live_blocks, n, device)
+        _check_block_flags('reached_blocks', reached_blocks, n, device)
+        scratch = (self._scratch_aux if aux else self._scratch)(n, settings, device)
         st = _lib.ForwardState(*state)
         self._check(self.lib.fgs_backward_reached(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
                                                   _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
                                                   _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
                                                   _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
                                                   _stream_of(device)),
-                    'fgs_backward_aux')
+                    'fgs_backward_aux' if aux else 'fgs_backward')
         return grads
-
-    def _scratch_aux(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
-        nbytes = int(self.lib.fgs_backward_aux_scratch_bytes(n, int(settings.width), int(settings.height)))
-        return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
 
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
                             buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,
@@ -318,17 +336,15 @@ class Backend:
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         keep: list = []
         n = params[0].shape[0]
-        total_rest = params[2].shape[1] if params[2].dim() == 3 else 0
-        S = self._settings(settings, total_rest, device, keep)
+        S = self._settings(settings, total_sh_rest(params[2]), device, keep)
         grad_image = grad_image.to(dtype=torch.float32).contiguous()
-        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
+        dens = _densification(densification_info, n, device, validate=False)
         scratch = self._scratch(n, settings, device)
         st = _lib.ForwardState(*state)
-        arr = lambda ts: (C.c_void_p * 6)(*[_ptr(t) for t in ts])
         lr_arr = (C.c_double * 6)(*[float(x) for x in lrs])
-        self._check(self.lib.fgs_backward_adam_fused(_ptr(grad_image), _ptr(image), arr(params), arr(exp_avgs), arr(exp_avg_sqs),
-                                                     _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]), _ptr(dens),
-                                                     scratch.data_ptr(), n, C.byref(S), C.byref(st), int(step), lr_arr,
+        self._check(self.lib.fgs_backward_adam_fused(_ptr(grad_image), _ptr(image), _pointer_array(params, 6), _pointer_array(exp_avgs, 6),
+                                                     _pointer_array(exp_avg_sqs, 6), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
+                                                     _ptr(buffers[3]), _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), int(step), lr_arr,
                                                      float(betas[0]), float(betas[1]), float(eps), _stream_of(device)),
                     'fgs_backward_adam_fused')
 
@@ -348,17 +364,16 @@ class Backend:
         if k == 0:
             return
         device = self._check_params(tuple(grads) + tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['adam tensor'] * (4 * k))
-        arr = lambda ts: (C.c_void_p * k)(*[_ptr(t) for t in ts])
         rows = None
         if live_blocks is not None or quiet_blocks is not None:
             n = params[0].shape[0]
             if any(p.dim() < 1 or p.shape[0] != n for p in params) or n == 0:
                 raise RuntimeError('live_blocks / quiet_blocks need parameter tensors that all have one row per Gaussian')
-            for name, flags in (('live_blocks', live_blocks), ('quiet_blocks', quiet_blocks)):
-                if flags is not None and (flags.dtype != torch.uint8 or flags.device != device or not flags.is_contiguous() or flags.numel() != (n + 63) // 64):
-                    raise RuntimeError(f'{name} must be a contiguous uint8 tensor of ceil(N / 64) elements on the parameters\' device')
+            _check_block_flags('live_blocks', live_blocks, n, device)
+            _check_block_flags('quiet_blocks', quiet_blocks, n, device)
             rows = (C.c_int32 * k)(*[p.numel() // n for p in params])
-        self._check(self.lib.fgs_adam_step_multi_quiet(k, arr(grads), arr(params), arr(exp_avgs), arr(exp_avg_sqs),
+        self._check(self.lib.fgs_adam_step_multi_quiet(k, _pointer_array(grads, k), _pointer_array(params, k), _pointer_array(exp_avgs, k),
+                                                       _pointer_array(exp_avg_sqs, k),
                                                        (C.c_int64 * k)(*[p.numel() for p in params]), (C.c_int32 * k)(*[int(s) for s in steps]),
                                                        (C.c_double * k)(*[float(x) for x in lrs]), float(beta1), float(beta2), float(eps),
                                                        _ptr(live_blocks), rows, _ptr(quiet_blocks), _stream_of(device)), 'fgs_adam_step_multi')
@@ -374,17 +389,16 @@ class Backend:
             raise RuntimeError('adam_quiet_scan needs moment tensors that all have one row per Gaussian')
         if out is None:
             out = torch.empty((n + 63) // 64, dtype=torch.uint8, device=device)
-        elif out.dtype != torch.uint8 or out.device != device or not out.is_contiguous() or out.numel() != (n + 63) // 64:
-            raise RuntimeError('quiet_blocks must be a contiguous uint8 tensor of ceil(N / 64) elements on the moments\' device')
-        arr = lambda ts: (C.c_void_p * k)(*[_ptr(t) for t in ts])
-        self._check(self.lib.fgs_adam_quiet_scan(k, arr(exp_avgs), arr(exp_avg_sqs), (C.c_int64 * k)(*[t.numel() for t in exp_avgs]),
+        else:
+            _check_block_flags('quiet_blocks', out, n, device, owner='moments')
+        self._check(self.lib.fgs_adam_quiet_scan(k, _pointer_array(exp_avgs, k), _pointer_array(exp_avg_sqs, k),
+                                                 (C.c_int64 * k)(*[t.numel() for t in exp_avgs]),
                                                  (C.c_int32 * k)(*[t.numel() // n for t in exp_avgs]), _ptr(out), _stream_of(device)),
                     'fgs_adam_quiet_scan')
         return out
 
-    def l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2,
-                 with_grad: bool = True):
-        """Fused photometric loss (Loss.py:15-16): returns (loss 0-dim tensor, dloss/dimage or None, (l1, ssim) tensor)."""
+    def _l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float, lambda_dssim: float, with_grad: bool) -> tuple:
+        """fgs_l1_dssim_loss: (sums = (l1, ssim, loss) formed on the device by the reduce kernel, dloss/dimage or None, the scratch with the derivative maps)."""
         device = self._check_params((image, target), ('image', 'target'))
         if image.dim() != 3 or image.shape[0] != 3 or image.shape != target.shape:
             raise RuntimeError('l1_dssim expects two [3,H,W] tensors')
@@ -394,19 +408,18 @@ class Backend:
         scratch = torch.empty(int(self.lib.fgs_l1_dssim_scratch_bytes(w, h)), dtype=torch.uint8, device=device)
         self._check(self.lib.fgs_l1_dssim_loss(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
                                                sums.data_ptr(), _ptr(grad), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_loss')
-        return sums[2], grad, sums[:2]      # loss and the (l1, ssim) means are formed on the device by the reduce kernel
+        return sums, grad, scratch
+
+    def l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2,
+                 with_grad: bool = True):
+        """Fused photometric loss (Loss.py:15-16): returns (loss 0-dim tensor, dloss/dimage or None, (l1, ssim) tensor)."""
+        sums, grad, _ = self._l1_dssim(image, target, lambda_l1, lambda_dssim, with_grad)
+        return sums[2], grad, sums[:2]
 
     def l1_dssim_forward(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2):
         """The loss value alone: returns (loss 0-dim tensor, (l1, ssim) tensor, scratch). `scratch` holds the derivative maps that
         l1_dssim_backward turns into dloss/dimage -- the shape of an autograd loss node (forward saves, backward launches one kernel)."""
-        device = self._check_params((image, target), ('image', 'target'))
-        if image.dim() != 3 or image.shape[0] != 3 or image.shape != target.shape:
-            raise RuntimeError('l1_dssim expects two [3,H,W] tensors')
-        _, h, w = image.shape
-        sums = torch.empty(3, dtype=torch.float32, device=device)
-        scratch = torch.empty(int(self.lib.fgs_l1_dssim_scratch_bytes(w, h)), dtype=torch.uint8, device=device)
-        self._check(self.lib.fgs_l1_dssim_loss(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
-                                               sums.data_ptr(), None, scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_loss')
+        sums, _, scratch = self._l1_dssim(image, target, lambda_l1, lambda_dssim, False)
         return sums[2], sums[:2], scratch
 
     def l1_dssim_backward(self, image: torch.Tensor, target: torch.Tensor, scratch: torch.Tensor, upstream: Optional[torch.Tensor] = None,
@@ -438,15 +451,14 @@ class Backend:
         """K1 over this rank's shard for all views of the step. `records`: uint8 [len(views), N, 56] (view v: the first
         counts[v, 0] records are filled), `counts`: int32 [len(views), 2] device tensor receiving (n_visible, n_instances).
         Returns the primitive buffer to hand to `shard_backward`."""
-        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_0', 'sh_coefficients_rest'))
+        device = self._check_params((means, scales, rotations, opacities, sh0, sh_rest), PARAMETER_NAMES)
         n, k = means.shape[0], len(views)
         if records.dtype != torch.uint8 or records.numel() < k * n * _lib.SPLAT_RECORD_BYTES or counts.dtype != torch.int32 \
                 or counts.numel() < 2 * k or records.device != device or counts.device != device or not records.is_contiguous() \
                 or not counts.is_contiguous():
             raise RuntimeError('records must be uint8 [views, N, 56] and counts int32 [views, 2] on the parameters\' device')
         keep: list = []
-        S = self._settings_array(views, sh_rest.shape[1] if sh_rest.dim() == 3 else 0, device, keep)
+        S = self._settings_array(views, total_sh_rest(sh_rest), device, keep)
         buffers, cb = self._make_resizer(device, 4)
         self._check(self.lib.fgs_shard_preprocess(_ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh0), _ptr(sh_rest), n, k,
                                                   S, _ptr(records), counts.data_ptr(), cb, None, _stream_of(device)), 'fgs_shard_preprocess')
@@ -459,15 +471,12 @@ class Backend:
         device = records.device
         if records.dtype != torch.uint8 or not records.is_contiguous() or records.numel() < n_records * _lib.SPLAT_RECORD_BYTES:
             raise RuntimeError('records must be a contiguous uint8 tensor of n_records * 56 bytes')
-        keep: list = []
-        S = self._settings(settings, total_sh_rest, device, keep)
+        S, keep, buffers, cb, st = self._forward_state(settings, total_sh_rest, device)
         image = torch.empty((3, settings.height, settings.width), dtype=torch.float32, device=device)
-        buffers, cb = self._make_resizer(device, 4)
-        st = _lib.ForwardState()
-        counts = (C.c_int32 * len(shard_counts))(*[int(c) for c in shard_counts]) if shard_counts else None
-        self._check(self.lib.fgs_forward_from_shard_records(_ptr(records), int(n_records), int(n_instances), counts, len(shard_counts) if shard_counts else 0,
+        counts, n_shards = _shard_counts(shard_counts)
+        self._check(self.lib.fgs_forward_from_shard_records(_ptr(records), int(n_records), int(n_instances), counts, n_shards,
                                                             C.byref(S), image.data_ptr(), cb, None, C.byref(st), _stream_of(device)), 'fgs_forward_from_shard_records')
-        return ForwardResult(image, tuple(buffers), (st.n_visible, st.n_instances, st.n_buckets, st.selector))
+        return ForwardResult(image, tuple(buffers), _state_tuple(st))
 
     def backward_to_records(self, grad_image, image, buffers, settings: RasterizerSettings, state, total_sh_rest: int,
                             out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None) -> torch.Tensor:
@@ -484,9 +493,9 @@ class Backend:
             raise RuntimeError('accumulator records must be contiguous float32 [n_records, 9]')
         scratch = self._scratch(n, settings, device)
         st = _lib.ForwardState(*state)
-        counts = (C.c_int32 * len(shard_counts))(*[int(c) for c in shard_counts]) if shard_counts else None
+        counts, n_shards = _shard_counts(shard_counts)
         self._check(self.lib.fgs_backward_to_shard_records(_ptr(grad_image), _ptr(image), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
-                                                           _ptr(buffers[3]), scratch.data_ptr(), _ptr(acc), n, counts, len(shard_counts) if shard_counts else 0,
+                                                           _ptr(buffers[3]), scratch.data_ptr(), _ptr(acc), n, counts, n_shards,
                                                            C.byref(S), C.byref(st), _stream_of(device)), 'fgs_backward_to_shard_records')
         return acc
 
@@ -494,22 +503,15 @@ class Backend:
                        scales, rotations, opacities, sh_rest, views: Sequence[RasterizerSettings], out: tuple) -> tuple:
         """K12 on the shard, gradients summed over `views`; `acc_records`: float32 [sum(n_visible), 9] in view order;
         `out` = the six gradient tensors (means, scales, rotations, opacities, sh0, sh_rest), every element written."""
-        device = self._check_params((means, scales, rotations, opacities, sh_rest) + tuple(out),
-                                    ('means', 'scales', 'rotations', 'opacities', 'sh_coefficients_rest') + ('grad',) * 6)
+        device = self._check_params((means, scales, rotations, opacities, sh_rest) + tuple(out), BACKWARD_PARAMETER_NAMES + ('grad',) * 6)
         n, k = means.shape[0], len(views)
-        total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
-        shapes = ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3))
-        for g, sh in zip(out, shapes):
-            if tuple(g.shape) != sh:
-                raise RuntimeError(f'preallocated gradient has shape {tuple(g.shape)}, expected {sh}')
-        total = int(sum(n_visible))
-        if len(n_visible) != k or (total > 0 and (acc_records.dtype != torch.float32 or acc_records.numel() < 9 * total
-                                                  or not acc_records.is_contiguous() or acc_records.device != device)):
-            raise RuntimeError('acc_records must be contiguous float32 [sum(n_visible), 9] and n_visible one entry per view')
+        total_rest = total_sh_rest(sh_rest)
+        _gradients_out(out, gradient_shapes(n, total_rest), device, shapes_only=True)
+        total = _check_acc_records(acc_records, n_visible, k, device)
         keep: list = []
         S = self._settings_array(views, total_rest, device, keep)
-        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
-        scratch = torch.empty(max(int(self.lib.fgs_shard_backward_scratch_bytes(n, k)), 1), dtype=torch.uint8, device=device)
+        dens = _densification(densification_info, n, device, validate=False)
+        scratch = _empty_bytes(self.lib.fgs_shard_backward_scratch_bytes(n, k), device)
         counts = (C.c_int32 * k)(*[int(x) for x in n_visible])
         self._check(self.lib.fgs_shard_backward(_ptr(acc_records) if total > 0 else None, counts, _ptr(primitive_buffer), _ptr(means),
                                                 _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(out[0]), _ptr(out[1]),
@@ -524,19 +526,15 @@ class Backend:
         optimizer-group order: means, sh0, sh_rest, opacities, scales, rotations."""
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         n, k = params[0].shape[0], len(views)
-        total_rest = params[2].shape[1] if params[2].dim() == 3 else 0
-        total = int(sum(n_visible))
-        if len(n_visible) != k or (total > 0 and (acc_records.dtype != torch.float32 or acc_records.numel() < 9 * total
-                                                  or not acc_records.is_contiguous() or acc_records.device != device)):
-            raise RuntimeError('acc_records must be contiguous float32 [sum(n_visible), 9] and n_visible one entry per view')
+        total = _check_acc_records(acc_records, n_visible, k, device)
         keep: list = []
-        S = self._settings_array(views, total_rest, device, keep)
-        dens = densification_info if densification_info is not None and densification_info.numel() > 0 else None
-        scratch = torch.empty(max(int(self.lib.fgs_shard_backward_scratch_bytes(n, k)), 1), dtype=torch.uint8, device=device)
+        S = self._settings_array(views, total_sh_rest(params[2]), device, keep)
+        dens = _densification(densification_info, n, device, validate=False)
+        scratch = _empty_bytes(self.lib.fgs_shard_backward_scratch_bytes(n, k), device)
         counts = (C.c_int32 * k)(*[int(x) for x in n_visible])
-        arr = lambda ts: (C.c_void_p * 6)(*[_ptr(t) for t in ts])
-        self._check(self.lib.fgs_shard_backward_adam_fused(_ptr(acc_records) if total > 0 else None, counts, _ptr(primitive_buffer), arr(params),
-                                                           arr(exp_avgs), arr(exp_avg_sqs), _ptr(dens), scratch.data_ptr(), n, k, S, int(step),
+        self._check(self.lib.fgs_shard_backward_adam_fused(_ptr(acc_records) if total > 0 else None, counts, _ptr(primitive_buffer),
+                                                           _pointer_array(params, 6), _pointer_array(exp_avgs, 6), _pointer_array(exp_avg_sqs, 6),
+                                                           _ptr(dens), scratch.data_ptr(), n, k, S, int(step),
                                                            (C.c_double * 6)(*[float(x) for x in lrs]), float(betas[0]), float(betas[1]),
                                                            float(eps), _stream_of(device)), 'fgs_shard_backward_adam_fused')
 
@@ -557,12 +555,12 @@ class Backend:
         op = old_opacities.to(torch.float32).contiguous()
         sc = old_scales.to(torch.float32).contiguous()
         ns = n_samples_per_primitive.to(device=device, dtype=torch.int64).contiguous()
-        table = getattr(self, '_relocation_table', {}).get(device)
+        table = self._relocation_table.get(device)
         if table is None:
             host = (C.c_float * 2500)()
             self._check(self.lib.fgs_relocation_table(host), 'fgs_relocation_table')
             table = torch.tensor(list(host), dtype=torch.float32, device=device)
-            self._relocation_table = {**getattr(self, '_relocation_table', {}), device: table}
+            self._relocation_table[device] = table
         n = op.shape[0]
         new_op = torch.empty((n, 1), dtype=torch.float32, device=device)
         new_sc = torch.empty((n, 3), dtype=torch.float32, device=device)
@@ -584,8 +582,8 @@ class Backend:
         copy, split). `noise_fn(n_rows)` supplies the [n_rows, 3] N(0,1) samples of the split (default torch.randn on the device)."""
         device = self._check_params(tuple(params) + (densification_info,), ['parameter'] * 6 + ['densification_info'])
         n = params[0].shape[0]
-        total_rest = params[2].shape[1] if params[2].dim() == 3 else 0
-        scratch = torch.empty(max(int(self.lib.fgs_adc_scratch_bytes(n)), 1), dtype=torch.uint8, device=device)
+        total_rest = total_sh_rest(params[2])
+        scratch = _empty_bytes(self.lib.fgs_adc_scratch_bytes(n), device)
         counts = (C.c_int32 * 4)()
         self._check(self.lib.fgs_adc_plan(_ptr(densification_info), _ptr(params[4]), _ptr(params[5]), _ptr(params[3]), n, float(grad_threshold),
                                           float(min_opacity), int(bool(prune_large_gaussians)), float(percent_dense), float(extent),
@@ -600,7 +598,7 @@ class Backend:
             self._check_params(tuple(exp_avgs) + tuple(exp_avg_sqs), ['moment'] * 12)
         out_m = [make(t) for t in params] if have_state else None
         out_v = [make(t) for t in params] if have_state else None
-        arr = lambda ts: (C.c_void_p * 6)(*[_ptr(t) for t in ts]) if ts is not None else None
+        arr = lambda ts: _pointer_array(ts, 6) if ts is not None else None
         self._check(self.lib.fgs_adc_apply(arr(params), arr(exp_avgs), arr(exp_avg_sqs), arr(out_p), arr(out_m), arr(out_v), _ptr(noise),
                                            scratch.data_ptr(), n, total_rest, _stream_of(device)), 'fgs_adc_apply')
         return out_p, out_m, out_v, (kept, clones, children, split)
@@ -617,7 +615,7 @@ class Backend:
             chunk, oc = tensors[first:first + 18], outs[first:first + 18]
             k = len(chunk)
             widths = [int(t.numel() // max(t.shape[0], 1)) if t.shape[0] > 0 else 0 for t in chunk]
-            self._check(self.lib.fgs_gather_rows(k, (C.c_void_p * k)(*[_ptr(t) for t in chunk]), (C.c_void_p * k)(*[_ptr(t) for t in oc]),
+            self._check(self.lib.fgs_gather_rows(k, _pointer_array(chunk, k), _pointer_array(oc, k),
                                                  (C.c_int32 * k)(*widths), _ptr(index), rows, _stream_of(device)), 'fgs_gather_rows')
         return outs
 

@@ -5,12 +5,15 @@ Renderer.py:72-123 runs unmodified against this package; the implementation unde
 """
 from __future__ import annotations
 
+import math
+import warnings
+import weakref
 from typing import Any
 
 import torch
 from torch.autograd.function import once_differentiable
 
-from ._backend import RasterizerSettings, default_backend
+from ._backend import RasterizerSettings, default_backend, gradient_shapes, total_sh_rest
 
 
 _GRAD_OUT = None   # optional provider of preallocated gradient tensors (harness/distributed.py packs them into one arena)
@@ -112,21 +115,13 @@ def clear_live_blocks(owned=None) -> None:
 
 
 def _gradient_arena(shapes, device):
+    numels = [math.prod(sh) for sh in shapes]
     offsets, total = [], 0
-    for sh in shapes:
+    for numel in numels:
         offsets.append(total)
-        numel = 1
-        for d in sh:
-            numel *= d
         total += (numel + _ALIGN_FLOATS - 1) // _ALIGN_FLOATS * _ALIGN_FLOATS
     arena = torch.empty(max(total, 1), dtype=torch.float32, device=device)
-    views = []
-    for sh, off in zip(shapes, offsets):
-        numel = 1
-        for d in sh:
-            numel *= d
-        views.append(arena[off:off + numel].view(sh))
-    return arena, tuple(views)
+    return arena, tuple(arena[off:off + numel].view(sh) for sh, off, numel in zip(shapes, offsets, numels))
 
 
 def match_live_blocks(gradients, owned=None) -> 'torch.Tensor | None':
@@ -219,7 +214,6 @@ def _view_ratio(A: dict, key, w2c: torch.Tensor) -> float:
 
 
 def _record_ratio(A: dict, key, w2c: torch.Tensor, ratio: float) -> None:
-    import weakref
     table = A['per_view']
     table.pop(key, None)
     table[key] = (ratio, weakref.ref(w2c), _tensor_version(w2c))
@@ -237,7 +231,6 @@ def _check_abandoned_passes(A: dict) -> None:
             continue
         del pending[ticket]
         if int(host[2]) != 0:
-            import warnings
             A['overflows'] += 1
             warnings.warn(f'FasterGS async forward: an earlier pass whose backward never ran needed {int(host[1])} instances but had capacity {capacity}: '
                           f'the image it returned was incomplete (render evaluation views under torch.no_grad(): those passes are sized synchronously)',
@@ -305,7 +298,6 @@ class _Rasterize(torch.autograd.Function):
             n = means.shape[0]
             _record_ratio(A, key, ctx.rasterizer_settings.w2c, int(host[1]) / max(n, 1))
             if int(host[2]) != 0:          # the capacity was too small: the image (and the loss gradient) missed the instances beyond it
-                import warnings
                 A['overflows'] += 1
                 warnings.warn(f'FasterGS async forward: {int(host[1])} instances exceeded the capacity {state[1]} of this pass: its image was '
                               f'incomplete, so this backward pass returns zero gradients and FusedAdam.step skips the step (the view is rendered with the '
@@ -317,29 +309,26 @@ class _Rasterize(torch.autograd.Function):
                     for z in zeros:
                         z.zero_()
                 else:
-                    total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
-                    zeros = tuple(torch.zeros(sh, dtype=torch.float32, device=means.device)
-                                  for sh in ((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3)))
+                    zeros = tuple(torch.zeros(sh, dtype=torch.float32, device=means.device) for sh in gradient_shapes(n, total_sh_rest(sh_rest)))
                 return (*zeros, None, None)
         n = means.shape[0]
-        if _LIVE['enabled'] and _GRAD_OUT is None and n > 0:
-            total_rest = sh_rest.shape[1] if sh_rest.dim() == 3 else 0
-            arena, views = _gradient_arena(((n, 3), (n, 3), (n, 4), (n, 1), (n, 1, 3), (n, total_rest, 3)), means.device)
+        handover = _LIVE['enabled'] and _GRAD_OUT is None and n > 0
+        if handover:
+            arena, out = _gradient_arena(gradient_shapes(n, total_sh_rest(sh_rest)), means.device)
             live, flags = torch.empty((2, (n + 63) // 64), dtype=torch.uint8, device=means.device)      # "any visible" / "any reached": the optimizer gets the latter
-            grads = default_backend().backward(ctx.densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest,
-                                               buffers, ctx.rasterizer_settings, state, out=views, live_blocks=live, reached_blocks=flags)
+        else:
+            clear_live_blocks([means])
+            out, live, flags = (_GRAD_OUT() if _GRAD_OUT is not None else None), None, None
+        grads = default_backend().backward(ctx.densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest,
+                                           buffers, ctx.rasterizer_settings, state, out=out, live_blocks=live, reached_blocks=flags)
+        if handover:
             slots = _LIVE['slots']
             slots.pop(means.data_ptr(), None)
             slots[means.data_ptr()] = {'arena': arena, 'version': arena._version, 'flags': flags,
-                                       'views': tuple((v.data_ptr() if v.numel() else 0, tuple(v.shape)) for v in views)}
+                                       'views': tuple((v.data_ptr() if v.numel() else 0, tuple(v.shape)) for v in out)}
             while len(slots) > _LIVE_MAX_SLOTS:          # models that backpropagate but never step: their arenas are not kept alive for ever
                 del slots[next(iter(slots))]
-            del views
-        else:
-            clear_live_blocks([means])
-            grads = default_backend().backward(ctx.densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest,
-                                               buffers, ctx.rasterizer_settings, state,
-                                               out=_GRAD_OUT() if _GRAD_OUT is not None else None)
+        del out          # the registry and this frame hold no view tensor: autograd adopts a gradient as `.grad` only if nobody else references it
         return (*grads, None, None)   # densification_info, rasterizer_settings
 
 
