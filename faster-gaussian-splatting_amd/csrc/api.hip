@@ -128,6 +128,37 @@ int run_forward(const ForwardRequest& rq) {
     return forward_tail(rq, pb, tb, geo, {rb->host[0], rb->host[1], depth_sel, false});
 }
 
+// K8+K9, and which tile -> workgroup mapping K10 runs with (ba.row_group, ba.tile_plan).
+#ifndef FGS_DEV_SWITCHES
+// The product: the training blend needs the per-tile bucket offsets for its checkpoints; always the columns mapping, which reads no plan.
+static int bucket_scan_and_mapping(bool training, const TileBuffers& tb, const Geometry& geo, BlendArgs& ba, hipStream_t stream) {
+    ba.row_group = kColumnsTopDown;
+    if (!training) return FGS_OK;
+    StageScope t(ST_BUCKET_SCAN, stream);
+    FGS_HIP(launch_plan_tiles(tb.ranges, tb.bucket_offsets, nullptr, geo.n_tiles, geo.grid_w, geo.grid_h, stream));
+    return FGS_OK;
+}
+#else
+// The dev library: the mapping is a process-wide A/B switch another thread may flip, so it is read ONCE per pass and travels in BlendArgs -- planning
+// and launch see the same value. The two mappings that read a device-side table get it from the scan's own kernel (binning_exhibits.hip), in inference
+// passes too; the library scan (option 11) makes none, and they fall back to the bands.
+static int bucket_scan_and_mapping(bool training, const TileBuffers& tb, const Geometry& geo, BlendArgs& ba, hipStream_t stream) {
+    ba.row_group = static_cast<uint32_t>(static_cast<int>(g_tile_row_group));
+    const bool need_plan = ba.row_group == kPlannedBlocks || ba.row_group == kBandsThroughPlan;
+    if (!training && !need_plan) return FGS_OK;
+    StageScope t(ST_BUCKET_SCAN, stream);
+    if (g_library_bucket_scan && training) {
+        FGS_HIP(run_bucket_scan(tb.temp, tb.temp_bytes, tb.ranges, tb.bucket_offsets, geo.n_tiles, stream));
+        if (need_plan) ba.row_group = 0u;
+        return FGS_OK;
+    }
+    uint32_t* const plan = need_plan ? tb.tile_plan : nullptr;
+    FGS_HIP(launch_plan_tiles(tb.ranges, tb.bucket_offsets, plan, geo.n_tiles, geo.grid_w, geo.grid_h, stream));
+    ba.tile_plan = plan;
+    return FGS_OK;
+}
+#endif
+
 // K2..K10 over a filled primitive buffer (rec, n_touched, depth keys + indices of the visible entries)
 int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffers& tb, const Geometry& geo, ForwardCounts counts) {
     const bool training = rq.mode == MODE_TRAINING;
@@ -155,24 +186,7 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
     ba.width = settings->width; ba.height = settings->height; ba.grid_w = geo.grid_w; ba.grid_h = geo.grid_h; ba.n_tiles = geo.n_tiles;
     ba.to_chw = rq.to_chw; ba.clamp_output = rq.clamp_output;
     uint32_t n_buckets_cap = 0;
-    // The tile -> workgroup mapping is read ONCE per pass and travels in BlendArgs, so that planning and launch see the same value (it is a
-    // process-wide A/B switch another thread may flip). K8+K9 (fwd:218-231) and K10's optional block plan are one single-workgroup kernel.
-    const uint32_t row_group = static_cast<uint32_t>(static_cast<int>(g_tile_row_group));
-    const bool need_plan = row_group == kPlannedBlocks || row_group == kBandsThroughPlan;     // A/B mappings that read a device-side table
-    const bool need_scan = training || need_plan;                                             // per-tile bucket offsets: the training blend's checkpoints
-    ba.row_group = row_group;
-    if (need_scan) {
-        StageScope t(ST_BUCKET_SCAN, stream);
-#ifdef FGS_DEV_SWITCHES
-        if (g_library_bucket_scan && training) {
-            FGS_HIP(run_bucket_scan(tb.temp, tb.temp_bytes, tb.ranges, tb.bucket_offsets, geo.n_tiles, stream));      // (A/B: rocPRIM scan, no plan)
-        } else
-#endif
-        {
-            FGS_HIP(launch_plan_tiles(tb.ranges, tb.bucket_offsets, need_plan ? tb.tile_plan : nullptr, geo.n_tiles, geo.grid_w, geo.grid_h, stream));
-            ba.tile_plan = need_plan ? tb.tile_plan : nullptr;
-        }
-    }
+    if (int rc = bucket_scan_and_mapping(training, tb, geo, ba, stream)) return rc;           // K8+K9 (fwd:218-231)
     BucketBuffers bb{};
     if (training) {
         // the bucket buffer sized by its bound (no read-back of n_buckets, fwd:234)

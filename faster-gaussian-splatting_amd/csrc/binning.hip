@@ -3,6 +3,7 @@
 //   -> stable tile sort on end_bit bits -> per-tile [start,end) ranges -> inclusive scan of per-tile bucket counts.
 // Semantics: reference rasterization/src/forward.cu:104-231 + kernels_forward.cuh:211-360 (two-stage "Splatshop" sort,
 // no 64-bit tile|depth key). Both sorts are radix_sort.hip; the offsets are a reduction + per-wave sums (below), the bucket scan a single-workgroup kernel.
+// The A/B exhibits of the chain (the library scan of the bucket counts, K10's device-side tile plan) are binning_exhibits.hip, dev library only.
 // Round 5: the depth sort's last scatter pass carries a 16-byte FOOTPRINT ROW per visible Gaussian (tile box + exact-overlap
 // bitmap, fgs_math.h) into depth order and writes its tile count beside it, so the scan (K3 + K4: apply_depth_ordering_cu + ExclusiveSum)
 // and the instance kernel (K5) read streams: until round 4 both gathered a 128-byte line per Gaussian for 4 / 16 useful bytes
@@ -12,10 +13,6 @@
 #include <fgs_wave.h>
 #include "fgs_tile_scan.h"
 #include <cstring>
-#ifdef FGS_DEV_SWITCHES
-#include <rocprim/device/device_scan.hpp>            // the library scan of the per-tile bucket counts: an A/B option of the dev build only
-#include <rocprim/iterator/transform_iterator.hpp>
-#endif
 
 namespace fgs {
 
@@ -356,129 +353,22 @@ hipError_t launch_extract_ranges(int key_bytes, const void* sorted_keys, uint2* 
     return hipGetLastError();
 }
 
-// ---- K8+K9 (kf:350-360 + fwd:225-231) + the tile -> workgroup plan of K10 ---------------------------------------------
+// ---- K8+K9 (kf:350-360 + fwd:225-231) -------------------------------------------------------------------------------------------
 // ONE single-workgroup kernel (fgs_tile_scan.h) replaces the library scan (rocPRIM look-back, 15 us for 12 k tiles):
-//  (1) bucket_offsets[t] = inclusive scan of ceil(len_t / 64)                                          (kf:350-360, fwd:225-231)
-//  (2) the plan that K10 reads to decide which tile a workgroup blends (blend_forward.hip: tile_of_workgroup).
-// Why a plan: the hardware deals workgroups to the 8 XCDs round-robin (XCD = workgroup % 8), every XCD has its own L2, and a
-// Gaussian's record is re-read by every tile it overlaps -- so an XCD should own compact pieces of the image. Round 1/2 gave every
-// XCD one contiguous band of tile rows: good locality, but the bands differ in work (at S2 the top band has 30 ms of summed tile time
-// against 44-47 ms for the others; on a layered scene 47 against 210-220: XCD 0 idles for two thirds of the kernel) and the heaviest
-// rows came last in every band (profiles/archive/r02_k10_timeline_before.txt). Interleaving single rows balances but gives up vertical
-// locality (+10 % layered, -9..16 % S2). The plan keeps both: the image is cut into 8 x 10 rectangular blocks of tiles (15 x 9 tiles
-// at 1080p: every XCD gets exactly 10 blocks, i.e. the same number of workgroups, which the round-robin deal requires); a block's
-// weight is its number of 64-Gaussian buckets (+ 1 per tile) -- known here, on the device, from the scan itself: no host read; the
-// blocks are sorted by weight and dealt in 10 rounds of 8, heaviest block of a round to the XCD with the least work so far; an XCD
-// walks its blocks in the order received = heaviest first, so the kernel's tail consists of the lightest blocks.
-__global__ void __launch_bounds__(kTileScanThreads) plan_tiles_kernel(const uint2* __restrict__ ranges, uint32_t* __restrict__ bucket_offsets,
-                                                                      uint32_t* __restrict__ tile_plan, const uint32_t n_tiles,
-                                                                      const uint32_t grid_w, const uint32_t grid_h, const int experiment) {
+// bucket_offsets[t] = inclusive scan of ceil(len_t / 64).
+__global__ void __launch_bounds__(kTileScanThreads) bucket_scan_kernel(const uint2* __restrict__ ranges, uint32_t* __restrict__ bucket_offsets,
+                                                                       const uint32_t n_tiles) {
     __shared__ TileScanShared s_scan;
-    __shared__ uint32_t s_weight[kPlanBlocks], s_sorted[kPlanBlocks];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    if (tid < kPlanBlocks) s_weight[tid] = 0u;
-    uint32_t base = 0;
-    int parity = 0;
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += kTileScanThreads * kTileScanPerThread, parity ^= 1) {   // one pass at 1080p (12 240 tiles)
-        uint32_t nb[kTileScanPerThread], ex[kTileScanPerThread];
-        const uint32_t first = t0 + tid * kTileScanPerThread;
-        if (first + kTileScanPerThread <= n_tiles) {                                         // 128 contiguous bytes: eight 16-byte loads
-            const uint4* q = reinterpret_cast<const uint4*>(ranges + first);
-#pragma unroll
-            for (int k = 0; k < kTileScanPerThread / 2; ++k) {
-                const uint4 r = q[k];
-                nb[2 * k] = (r.y - r.x + kBucket - 1) / kBucket;                              // kf:350-360
-                nb[2 * k + 1] = (r.w - r.z + kBucket - 1) / kBucket;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kTileScanPerThread; ++k) {
-                uint2 r = make_uint2(0u, 0u);
-                if (first + k < n_tiles) r = ranges[first + k];
-                nb[k] = (r.y - r.x + kBucket - 1) / kBucket;
-            }
-        }
-        const uint32_t total = tile_scan_pass(nb, ex, s_scan, base, parity);
-        if (first + kTileScanPerThread <= n_tiles) {
-            uint4* o = reinterpret_cast<uint4*>(bucket_offsets + first);                      // inclusive (fwd:225-231)
-#pragma unroll
-            for (int k = 0; k < kTileScanPerThread / 4; ++k)
-                o[k] = make_uint4(ex[4 * k] + nb[4 * k], ex[4 * k + 1] + nb[4 * k + 1], ex[4 * k + 2] + nb[4 * k + 2], ex[4 * k + 3] + nb[4 * k + 3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kTileScanPerThread; ++k) if (first + k < n_tiles) bucket_offsets[first + k] = ex[k] + nb[k];
-        }
-        base += total;
-    }
-    if (tile_plan == nullptr) return;                                                        // the default mapping of K10 is closed-form: no plan
-    __syncthreads();                                                                         // bucket_offsets visible to the workgroup
-    // block weights: one (block, tile row) pair per work item -- a difference of two scan values
-    const uint32_t bw = (grid_w + kPlanBlocksX - 1) / kPlanBlocksX, bh = (grid_h + kPlanBlocksY - 1) / kPlanBlocksY;
-    for (uint32_t i = tid; i < kPlanBlocks * bh; i += kTileScanThreads) {
-        const uint32_t b = i / bh, r = i - b * bh;
-        const uint32_t bx = b % kPlanBlocksX, by = b / kPlanBlocksX;
-        const uint32_t ty = by * bh + r, x0 = bx * bw, x1 = min(x0 + bw, grid_w);
-        if (ty < grid_h && x0 < x1) {
-            const uint32_t last = ty * grid_w + x1 - 1u, first = ty * grid_w + x0;
-            const uint32_t w = bucket_offsets[last] - (first != 0u ? bucket_offsets[first - 1u] : 0u) + (x1 - x0);
-            atomicAdd(&s_weight[b], w);
-        }
-    }
-    __syncthreads();
-    // sort the blocks by weight (descending, ties by index): rank by counting -- 80 broadcast reads per thread
-    if (tid < kPlanBlocks) {
-        const uint32_t w = s_weight[tid];
-        uint32_t rank = 0;
-        for (uint32_t o = 0; o < kPlanBlocks; ++o) {
-            const uint32_t wo = s_weight[o];
-            rank += (wo > w || (wo == w && o < tid)) ? 1u : 0u;
-        }
-        s_sorted[(experiment & 1) ? tid : rank] = tid;                                       // experiment bit 0: no sort (blocks in natural order)
-    }
-    __syncthreads();
-    if (tid < kWave) {                                                                       // wave 0: the deal, lanes 0..7 = the XCDs
-        uint32_t load = 0;
-        for (uint32_t round = 0; round < kPlanBlocksPerXcd; ++round) {
-            uint32_t rank = 0;                                                               // my position among the XCDs by work so far
-#pragma unroll
-            for (int x = 0; x < kXcds; ++x) {
-                const uint32_t lx = wave_read(load, x);
-                rank += (lx < load || (lx == load && static_cast<uint32_t>(x) < lane)) ? 1u : 0u;
-            }
-            if (experiment & 1) rank = lane;                                                 // ... dealt statically: XCD x owns block column x
-            if (lane < kXcds) {
-                const uint32_t b = s_sorted[round * kXcds + rank];                           // least work so far <- heaviest block of the round
-                load += s_weight[b];
-                tile_plan[kPlanHeader + lane * kPlanBlocksPerXcd + round] = b;
-            }
-        }
-        if (lane == 0) { tile_plan[0] = bw; tile_plan[1] = bh; tile_plan[2] = bw * bh; tile_plan[3] = kPlanBlocksPerXcd; }
-    }
+    scan_bucket_counts(ranges, bucket_offsets, n_tiles, s_scan);
 }
 
 hipError_t launch_plan_tiles(const uint2* ranges, uint32_t* bucket_offsets, uint32_t* tile_plan, uint32_t n_tiles, uint32_t grid_w, uint32_t grid_h,
                              hipStream_t s) {
-    hipLaunchKernelGGL(plan_tiles_kernel, dim3(1), dim3(kTileScanThreads), 0, s, ranges, bucket_offsets, tile_plan, n_tiles, grid_w, grid_h,
-                       static_cast<int>(g_plan_experiment));
+#ifdef FGS_DEV_SWITCHES
+    if (tile_plan != nullptr) return launch_plan_tiles_exhibit(ranges, bucket_offsets, tile_plan, n_tiles, grid_w, grid_h, s);   // K10's A/B mappings that read a plan
+#endif
+    hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(kTileScanThreads), 0, s, ranges, bucket_offsets, n_tiles);
     return hipGetLastError();
 }
-
-#ifdef FGS_DEV_SWITCHES
-// the library scan (rocPRIM): kept for A/B runs (fgs_debug_set_option(11, 1))
-struct BucketsOfRange {
-    __host__ __device__ uint32_t operator()(const uint2& r) const { return (r.y - r.x + kBucket - 1) / kBucket; }
-};
-size_t bucket_scan_temp_bytes(uint32_t n_tiles) {
-    size_t bytes = 0;
-    auto in = rocprim::make_transform_iterator(static_cast<const uint2*>(nullptr), BucketsOfRange{});
-    (void)rocprim::inclusive_scan(nullptr, bytes, in, static_cast<uint32_t*>(nullptr), n_tiles, rocprim::plus<uint32_t>());
-    return bytes;
-}
-hipError_t run_bucket_scan(void* temp, size_t temp_bytes, const uint2* ranges, uint32_t* bucket_offsets, uint32_t n_tiles, hipStream_t s) {
-    auto in = rocprim::make_transform_iterator(ranges, BucketsOfRange{});
-    return rocprim::inclusive_scan(temp, temp_bytes, in, bucket_offsets, n_tiles, rocprim::plus<uint32_t>(), s);
-}
-
-#endif  // FGS_DEV_SWITCHES
 
 }  // namespace fgs

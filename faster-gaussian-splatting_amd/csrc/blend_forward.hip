@@ -9,116 +9,21 @@
 //  * Gaussians are staged 192 at a time through LDS from ONE 48-byte record per primitive (3 x 16-B loads from one line).
 //  * checkpoints are written every kBucket=64 Gaussians (one backward wavefront) -- half the reference's checkpoint
 //    traffic -- 1 KiB contiguous per wave; T_final / n_processed are tile-major so backward reads them coalesced.
-//  * workgroup -> tile mapping keeps contiguous image bands on one XCD (workgroup b runs on XCD b % 8), so the
-//    records gathered by neighbouring tiles stay in that XCD's 4 MiB L2.
+//  * workgroup -> tile mapping keeps one vertical strip of the image on one XCD (workgroup b runs on XCD b % 8), so the
+//    records gathered by neighbouring tiles stay in that XCD's 4 MiB L2 (fgs_k10_mappings.h: tile_of_workgroup).
 #include <atomic>
 
 #include "fgs_kernels.h"
 #include <fgs_wave.h>
+#include "fgs_k10_probes.h"      // FGS_K10_PROBE_*: empty unless a probe library is being built
 
 #ifndef FGS_CKPT_NT
 #define FGS_CKPT_NT 1      // round 6: K10's checkpoints -- written once, read once by K11 a millisecond later -- leave as non-temporal stores (training iteration 2.218 -> 2.187 ms, layered scene 3.728 -> 3.706, three alternating pairs: profiles/r06_ab_ckpt_nt.txt); 0: A/B
 #endif
+#include "fgs_k10_mappings.h"   // tile_of_workgroup, blend_grid: which tile a workgroup blends (BlendArgs::row_group; the product passes kColumnsTopDown)
+
 namespace fgs {
 
-// Which tile does workgroup `block` blend? The hardware deals workgroups to the 8 XCDs round-robin (XCD = block % 8), and a Gaussian's
-// records are re-read by every tile it overlaps -- from the XCD's own L2 if the neighbouring tiles run there. Round 1 gave every XCD one
-// contiguous band of tile rows. A per-tile timeline (tools/k10_timeline.sh, profiles/archive/r02_k10_timeline_before.txt) showed what that costs: the
-// top band of the image is nearly empty (XCD 0 had 30 ms of summed tile time against 44-47 ms for the others at S2, 47 against 210-220 ms on the
-// layered scene, and idled for a third / two thirds of the kernel), and the heaviest rows -- the bottom of the image, nearest to the camera --
-// came LAST in every band. Alternative mapping (row_group >= 1): groups of `row_group` consecutive tile rows are dealt to the XCDs in turn over
-// the whole image and every XCD walks its rows from the bottom of the image upwards (heaviest first). Measured (tools/ab_tile_rows.py,
-// profiles/archive/r02_ab_tile_rows.txt; training / inference blend): S2 bands 0.163 / 0.157 ms, g = 1 0.177 / 0.171, g = 2 0.189 / 0.182 -- at two
-// blended buckets per tile the kernel lives on the L2 locality of vertical neighbours; layered scene (11 buckets per tile) bands 0.725 / 0.700,
-// g = 1 0.663 / 0.646, g = 2 0.654 / 0.633 -- there balance wins 10 %. Bands walked bottom-up (255): no difference. Which of the two a scene
-// wants depends on how deep its tiles blend, which the host does not know at launch: the DEFAULT stays the bands (the benchmark workload),
-// fgs_debug_set_option(10, g) selects the other. Returns n_tiles for padding workgroups.
-// Round 3, measured on one box (tools/ab_tile_plan.py, profiles/archive/r03_ab_tile_plan.txt; training blend S2 / layered scene, ms):
-//   bands (round 1/2 default)                          0.168 / 0.765
-//   single rows interleaved                            0.179 / 0.657
-//   8 x 10 blocks weighed on the device by their bucket counts, sorted, dealt heaviest-first to the least-loaded XCD
-//   (row_group == kPlannedBlocks, plan_tiles_kernel)   0.181 / 0.646   -- balance, but the scattered block order costs S2 what rows cost
-//   the same blocks in natural order, XCD x = block column x          0.164 / 0.673
-//   COLUMNS (kColumnsTopDown, the default now): XCD x owns the vertical strip of tile columns [x w, (x + 1) w), w = ceil(grid_w / 8),
-//   and walks it row by row from the top                              0.164 / 0.669   (bottom-up: 0.177 / 0.695)
-// The work gradient of a rendered view is vertical (sky on top, near ground at the bottom), so a vertical strip per XCD is balanced by
-// construction and as compact as a band: -2 % at S2 and -12 % on the layered scene against the bands, closed form, no device data. The
-// device-side plan stays as an A/B option (it wins 3 % more on the layered scene and loses 10 % at S2).
-constexpr unsigned kBandsBottomFirst = 255u;     // row_group value: the round-1 bands, each walked from its last tile to its first
-__device__ __forceinline__ unsigned tile_of_workgroup(const unsigned block, const unsigned grid_w, const unsigned n_tiles, const unsigned row_group,
-                                                      const uint32_t* __restrict__ plan = nullptr, const unsigned grid_h = 0u) {
-    if (row_group == kPlannedBlocks) {
-        const unsigned bw = (grid_w + kPlanBlocksX - 1) / kPlanBlocksX, bh = (grid_h + kPlanBlocksY - 1) / kPlanBlocksY;   // = plan[0], plan[1]
-        const unsigned per_block = bw * bh;
-        const unsigned xcd = block % kXcds, q = block / kXcds;
-        const unsigned slot = q / per_block, local = q - slot * per_block;
-        if (slot >= kPlanBlocksPerXcd) return n_tiles;
-        const unsigned b = plan[kPlanHeader + xcd * kPlanBlocksPerXcd + slot];                 // wave-uniform: a scalar load
-        const unsigned ly = local / bw, lx = local - ly * bw;
-        const unsigned tx = (b % kPlanBlocksX) * bw + lx, ty = (b / kPlanBlocksX) * bh + ly;
-        return (tx < grid_w && ty < grid_h) ? ty * grid_w + tx : n_tiles;
-    }
-    if (row_group == kColumnsTopDown || row_group == kColumnsBottomUp) {
-        // every XCD owns one vertical strip of the image, ceil(grid_w / 8) tiles wide, and walks it row by row: compact (the strip's rows
-        // follow each other in time, so a Gaussian's record is still in this XCD's L2 when the row below needs it), and balanced by
-        // construction against the dominant work gradient of a rendered scene -- the vertical one (sky / far background on top, near
-        // ground at the bottom): every XCD gets every image row
-        const unsigned bw = (grid_w + kXcds - 1) / kXcds;
-        const unsigned xcd = block % kXcds, q = block / kXcds;
-        const unsigned r = q / bw, c = q - r * bw;
-        const unsigned tx = xcd * bw + c, ty = row_group == kColumnsTopDown ? r : grid_h - 1u - r;
-        return (tx < grid_w && r < grid_h) ? ty * grid_w + tx : n_tiles;
-    }
-    if (row_group == kBandsThroughPlan) {                                                   // A/B: what does the plan's load alone cost?
-        const unsigned per_xcd = (n_tiles + kXcds - 1) / kXcds;
-        const unsigned tile = (block % kXcds) * per_xcd + block / kXcds + (plan[kPlanHeader + (block % kXcds) * kPlanBlocksPerXcd] >> 30);
-        return tile < n_tiles ? tile : n_tiles;
-    }
-    if (row_group == 0u || row_group == kBandsBottomFirst) {                                // one contiguous band per XCD, top-down or bottom-up
-        const unsigned per_xcd = (n_tiles + kXcds - 1) / kXcds;
-        const unsigned idx = block / kXcds;
-        const unsigned tile = (block % kXcds) * per_xcd + (row_group == 0u ? idx : per_xcd - 1u - idx);
-        return tile < n_tiles ? tile : n_tiles;
-    }
-    const unsigned n_rows = n_tiles / grid_w;
-    const unsigned xcd = block % kXcds, j = block / kXcds;
-    const unsigned k = j / grid_w, col = j - k * grid_w;                                   // k-th row this XCD walks
-    const unsigned cycles = (n_rows + kXcds * row_group - 1) / (kXcds * row_group);        // groups per XCD
-    if (k >= cycles * row_group) return n_tiles;
-    const unsigned kk = cycles * row_group - 1u - k;                                       // bottom of the image first
-    const unsigned row = (kk / row_group) * (kXcds * row_group) + xcd * row_group + kk % row_group;
-    return row < n_rows ? row * grid_w + col : n_tiles;
-}
-// Round 5 tried the strips as per-XCD QUEUES with stealing (a workgroup pops the next tile of the strip of the XCD it runs on, hardware XCC_ID, and takes
-// from the fullest other strip once its own is empty) for object-centric scenes, whose outer strips are nearly empty (bench.py's surface scene: 5.8 ms of
-// summed tile time on XCD 0 against 108 ms on XCD 3). Measured (tools/ab_k10_mapping.py at the commit that had it): the one returning atomic per workgroup
-// costs S2 0.145 -> 0.176 ms (10 800 pops onto eight words), a device-scope snapshot of the queue heads in front of it 0.73 ms; and the scene that
-// motivated it gains nothing from balance alone -- the device-side block plan, which balances it, measures 0.366 against 0.387 ms -- because its span is
-// the serial walk of single tiles with lists of thousands (389 us for one tile of 3 860 walked entries). Removed.
-static unsigned blend_grid(const BlendArgs& a) {
-    if (a.row_group == kColumnsTopDown || a.row_group == kColumnsBottomUp) return kXcds * ((a.grid_w + kXcds - 1) / kXcds) * a.grid_h;
-    if (a.row_group == kBandsThroughPlan) return ((a.n_tiles + kXcds - 1) / kXcds) * kXcds;
-    if (a.row_group == kPlannedBlocks)
-        return kPlanBlocks * ((a.grid_w + kPlanBlocksX - 1) / kPlanBlocksX) * ((a.grid_h + kPlanBlocksY - 1) / kPlanBlocksY);
-    if (a.row_group == 0u || a.row_group == kBandsBottomFirst) return ((a.n_tiles + kXcds - 1) / kXcds) * kXcds;
-    const unsigned grid_h = a.n_tiles / a.grid_w;
-    const unsigned cycles = (grid_h + kXcds * a.row_group - 1) / (kXcds * a.row_group);
-    return kXcds * cycles * a.row_group * a.grid_w;
-}
-
-// Debug-only timeline (tools/k10_timeline.sh builds a separate library with -DFGS_K10_TIMELINE; the product build has none of it): per tile
-// its start / end on the chip-wide 100 MHz counter, the length of its list and how far it was walked.
-#ifdef FGS_K10_TIMELINE
-constexpr unsigned kK10TimelineTiles = 1u << 17;
-__device__ unsigned long long g_k10_timeline[kK10TimelineTiles * 4];
-#endif
-
-// Debug-only pair statistics (tools/pair_stats.sh, -DFGS_PAIR_STATS; the product build has none of it): [0] tiles, [1] instances staged, [2] (Gaussian,
-// 16x4 strip) pairs walked (the union of the two sub-tile masks), [3] lanes of walked pairs whose own 8x4 sub-tile is hit and whose pixel is not finished,
-// [4] lanes that blended (alpha test passed), [5] (Gaussian, strip) slots offered to the cull = 64-Gaussian chunks x 64 seen by a wave that still had a live pixel.
-#ifdef FGS_PAIR_STATS
-__device__ unsigned long long g_k10_pair_stats[8];
-#endif
 // AUX (inference only, fgs_inference_aux): the same walk also yields per pixel the accumulated opacity 1 - T, the expected depth sum_i w_i z_i and the
 // median depth (z of the last blended Gaussian met with T > 0.5), z = view_depth of the Gaussian's mean -- the value behind K1's depth key. z takes the
 // seat of the record's hit_mask word in the staged third row, which the blend never reads: it is computed where the record is fetched (the staging and
@@ -133,9 +38,7 @@ template <bool TRAINING, bool AUX>
 __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_d = nullptr) {
     const unsigned tile = tile_of_workgroup(blockIdx.x, a.grid_w, a.n_tiles, a.row_group, a.tile_plan, a.grid_h);
     if (tile >= a.n_tiles) return;
-#ifdef FGS_K10_TIMELINE
-    const unsigned long long t_start_ = __builtin_amdgcn_s_memrealtime();
-#endif
+    FGS_K10_PROBE_TILE_BEGIN()
     const unsigned tile_x = tile % a.grid_w, tile_y = tile / a.grid_w;
     const unsigned tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u, half = lane >> 5;
     const unsigned lx = half * kSubtileW + (lane & 7u), ly = wave * kSubtileH + ((lane >> 3) & 3u);
@@ -162,9 +65,6 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_
     float4* const s_c = s_rec + 2 * kBlendBlock;                      // b bounds_x bounds_y -
     __shared__ unsigned s_max[kBlendBlock / kWave];
 
-#ifdef FGS_PAIR_STATS
-    unsigned st_staged = 0, st_pairs = 0, st_mine = 0, st_pass = 0, st_offered = 0;
-#endif
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, T = 1.0f;
     float depth_sum = 0.0f, depth_med = 0.0f;                          // AUX
     Camera cam;                                                        // AUX: the third row of w2c is all view_depth reads (wave-uniform scalar loads)
@@ -241,10 +141,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_
             const uint64_t mine = inside ? (half ? mask_r : mask_l) : 0ull;            // pixels outside the image never blend
             uint64_t pending = mask_l | mask_r;
             if (wave_ballot(!done) == 0) pending = 0;
-#ifdef FGS_PAIR_STATS
-            if (wave == 0) st_staged += min(static_cast<unsigned>(kBucket), batch - chunk);
-            if (wave_ballot(!done) != 0) st_offered += min(static_cast<unsigned>(kBucket), batch - chunk);
-#endif
+            FGS_K10_PROBE_CHUNK(wave, done, batch, chunk)
             // The walk over the set bits saturates the scalar unit (ONE per CU for four SIMDs; rocprofv3 on the layered scene, round 2:
             // SQ_INSTS_SALU = SQ_INSTS_VALU = 457 M per launch), so every test of a (pixel, Gaussian) pair is ONE vector compare:
             //  * the 64-bit list is walked as two bit-reversed 32-bit words from the top (count-leading-zeros / clear on single registers);
@@ -288,11 +185,8 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_
                     const float alpha2 = hb.y * gauss2;
                     const float tested = __uint_as_float(((not_mine << k) & 0x80000000u) | __float_as_uint(alpha));
                     const float tested2 = __uint_as_float(((not_mine << k2) & 0x80000000u) | __float_as_uint(alpha2));
-#ifdef FGS_PAIR_STATS
-                    st_pairs += second ? 2u : 1u;
-                    st_mine += static_cast<unsigned>(__popcll(wave_ballot(((not_mine << k) & 0x80000000u) == 0u && gate < 1.0f)));
-                    st_pass += static_cast<unsigned>(__popcll(wave_ballot(tested >= gate)));
-#endif
+                    FGS_K10_PROBE_TRIP(second)
+                    FGS_K10_PROBE_ENTRY(not_mine, k, gate, tested)
                     if (tested >= gate) {
                         const float w = T * alpha;
                         cr += w * gb.z; cg += w * gb.w; cb += w * blue;
@@ -302,10 +196,7 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_
                         n_used = batch_start + j0 + k + 1;                             // kf:474
                     }
                     if (second) {
-#ifdef FGS_PAIR_STATS
-                        st_mine += static_cast<unsigned>(__popcll(wave_ballot(((not_mine << k2) & 0x80000000u) == 0u && gate < 1.0f)));
-                        st_pass += static_cast<unsigned>(__popcll(wave_ballot(tested2 >= gate)));
-#endif
+                        FGS_K10_PROBE_ENTRY(not_mine, k2, gate, tested2)
                         if (tested2 >= gate) {
                             const float w = T * alpha2;
                             cr += w * hb.z; cg += w * hb.w; cb += w * blue2;
@@ -347,55 +238,13 @@ __device__ __forceinline__ void blend_tile(const BlendArgs a, float* const ckpt_
         __syncthreads();
         if (tid == 0) a.max_n_processed[tile] = max(s_max[0], max(s_max[1], s_max[2]));   // kf:493-497
     }
-#ifdef FGS_PAIR_STATS
-    if (TRAINING && lane == 0) {
-        if (wave == 0) { atomicAdd(&g_k10_pair_stats[0], 1ull); atomicAdd(&g_k10_pair_stats[1], static_cast<unsigned long long>(st_staged)); }
-        atomicAdd(&g_k10_pair_stats[2], static_cast<unsigned long long>(st_pairs)); atomicAdd(&g_k10_pair_stats[3], static_cast<unsigned long long>(st_mine));
-        atomicAdd(&g_k10_pair_stats[4], static_cast<unsigned long long>(st_pass)); atomicAdd(&g_k10_pair_stats[5], static_cast<unsigned long long>(st_offered));
-    }
-#endif
-#ifdef FGS_K10_TIMELINE
-    if (tid == 0 && tile < kK10TimelineTiles) {
-        g_k10_timeline[tile * 4u] = t_start_;
-        g_k10_timeline[tile * 4u + 1u] = __builtin_amdgcn_s_memrealtime();
-        g_k10_timeline[tile * 4u + 2u] = (static_cast<unsigned long long>(n_total) << 32) | blockIdx.x;
-        g_k10_timeline[tile * 4u + 3u] = static_cast<unsigned long long>(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)));   // XCC_ID
-    }
-#endif
+    FGS_K10_PROBE_TILE_END(TRAINING, tid, wave, lane, tile, n_total)
 }
 
 template <bool TRAINING>
 __global__ void __launch_bounds__(kBlendBlock) blend_kernel(const BlendArgs a) { blend_tile<TRAINING, false>(a); }
 __global__ void __launch_bounds__(kBlendBlock) blend_aux_kernel(const BlendArgs a) { blend_tile<false, true>(a); }
 __global__ void __launch_bounds__(kBlendBlock) blend_training_aux_kernel(const BlendDepthArgs a) { blend_tile<true, true>(a.blend, a.ckpt_d); }
-
-#ifdef FGS_K10_TIMELINE
-}  // namespace fgs
-extern "C" __attribute__((visibility("default"))) int fgs_debug_k10_timeline(unsigned long long* out, unsigned n_tiles, int reset) {
-    if (n_tiles > fgs::kK10TimelineTiles) n_tiles = fgs::kK10TimelineTiles;
-    if (out != nullptr && hipMemcpyFromSymbol(out, HIP_SYMBOL(fgs::g_k10_timeline), sizeof(unsigned long long) * 4 * n_tiles) != hipSuccess) return -1;
-    if (reset) {
-        void* dev = nullptr;
-        if (hipGetSymbolAddress(&dev, HIP_SYMBOL(fgs::g_k10_timeline)) != hipSuccess
-            || hipMemset(dev, 0, sizeof(unsigned long long) * 4 * fgs::kK10TimelineTiles) != hipSuccess) return -1;
-    }
-    return 0;
-}
-namespace fgs {
-#endif
-
-#ifdef FGS_PAIR_STATS
-}  // namespace fgs
-extern "C" __attribute__((visibility("default"))) int fgs_debug_k10_pair_stats(unsigned long long* out, int reset) {
-    if (out != nullptr && hipMemcpyFromSymbol(out, HIP_SYMBOL(fgs::g_k10_pair_stats), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        void* dev = nullptr;
-        if (hipGetSymbolAddress(&dev, HIP_SYMBOL(fgs::g_k10_pair_stats)) != hipSuccess || hipMemset(dev, 0, sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    }
-    return 0;
-}
-namespace fgs {
-#endif
 
 // Speedy-Splat pruning scores (kernels_pruning_scores.cuh:348-505): the tile list is blended twice -- pass 1
 // for the final colour / transmittance, pass 2 re-walks it with dL/dC = 1 and adds (opacity * dL/dalpha)^2 of every blended
@@ -481,32 +330,25 @@ __global__ void __launch_bounds__(kBlendBlock) pruning_scores_kernel(const Blend
 #undef FGS_PIXEL_DONE
 }
 
-hipError_t launch_pruning_scores(const BlendArgs& a_in, hipStream_t s) {
-    BlendArgs a = a_in;                          // row_group: set by the caller (api.hip: forward_tail reads the switch once per pass)
-    if (a.tile_plan == nullptr && (a.row_group == kPlannedBlocks || a.row_group == kBandsThroughPlan)) a.row_group = 0u;
+// The launchers: one workgroup per tile and the mapping's padding (blend_grid). The mapping itself is the caller's (BlendArgs::row_group).
+hipError_t launch_pruning_scores(const BlendArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(pruning_scores_kernel, dim3(blend_grid(a)), dim3(kBlendBlock), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_blend(bool training, const BlendArgs& a_in, hipStream_t s) {
-    BlendArgs a = a_in;                          // row_group: set by the caller (api.hip: forward_tail reads the switch once per pass)
-    if (a.tile_plan == nullptr && (a.row_group == kPlannedBlocks || a.row_group == kBandsThroughPlan)) a.row_group = 0u;          // no plan was made: the bands
+hipError_t launch_blend(bool training, const BlendArgs& a, hipStream_t s) {
     const dim3 grid(blend_grid(a)), block(kBlendBlock);
     if (training) hipLaunchKernelGGL(blend_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(blend_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_blend_aux(const BlendArgs& a_in, hipStream_t s) {
-    BlendArgs a = a_in;
-    if (a.tile_plan == nullptr && (a.row_group == kPlannedBlocks || a.row_group == kBandsThroughPlan)) a.row_group = 0u;
+hipError_t launch_blend_aux(const BlendArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(blend_aux_kernel, dim3(blend_grid(a)), dim3(kBlendBlock), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_blend_training_aux(const BlendDepthArgs& a_in, hipStream_t s) {
-    BlendDepthArgs a = a_in;
-    if (a.blend.tile_plan == nullptr && (a.blend.row_group == kPlannedBlocks || a.blend.row_group == kBandsThroughPlan)) a.blend.row_group = 0u;
+hipError_t launch_blend_training_aux(const BlendDepthArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(blend_training_aux_kernel, dim3(blend_grid(a.blend)), dim3(kBlendBlock), 0, s, a);
     return hipGetLastError();
 }

@@ -59,7 +59,7 @@ constexpr int kSplatRecordWords = 14;          // sharded path: PrimRec (12 word
 constexpr int kMaxBatchViews = 8;              // sharded path: views handled by one K1 / K12 launch (grid.y / in-kernel loop)
 constexpr int kAccRecordWords = 9;             // sharded path: the 9 pixel-space accumulators = FGS_ACC_RECORD_BYTES / 4
 constexpr int kXcds = 8;                       // tile -> workgroup mapping keeps compact pieces of the image on one XCD's L2
-// K10's tile plan (binning.hip: plan_tiles_kernel): the tile grid is cut into kPlanBlocksX x kPlanBlocksY rectangular blocks, dealt to the
+// K10's tile plan (dev library; binning_exhibits.hip: plan_tiles_kernel): the tile grid is cut into kPlanBlocksX x kPlanBlocksY rectangular blocks, dealt to the
 // XCDs by weight; tile_plan = [block width, block height, tiles per block, blocks per XCD, then the block ids of XCD 0, XCD 1, ...]
 constexpr unsigned kPlanBlocksX = 8, kPlanBlocksY = 10, kPlanBlocks = kPlanBlocksX * kPlanBlocksY;
 constexpr unsigned kPlanBlocksPerXcd = kPlanBlocks / kXcds;

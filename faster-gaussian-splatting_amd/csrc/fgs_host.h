@@ -78,14 +78,14 @@ struct PrimitiveBuffers {             // cf. bu:45-94
 };
 struct TileBuffers {                  // cf. bu:126-152; final_T / n_processed are tile-major here
     uint2* ranges; uint32_t* bucket_offsets; uint32_t* max_n_processed; float* final_T; uint32_t* n_processed;
-    uint32_t* tile_plan;              // K10's tile -> workgroup plan (plan_tiles_kernel)
+    uint32_t* tile_plan;              // K10's tile -> workgroup plan (dev library: plan_tiles_kernel); carved in both flavours, the blob layout is one
     uint32_t* live_count;             // backward: number of live buckets (K11 planning pass)
     uint32_t* live_offsets;           // backward: first slot of each tile in the live-bucket list
     char* temp; size_t temp_bytes;
     static TileBuffers carve(Carver& c, uint32_t t, bool training) {
         TileBuffers b{};
         b.ranges = c.take<uint2>("ranges", t);
-        b.bucket_offsets = c.take<uint32_t>("bucket_offsets", t);         // inference too: the plan's block weights are differences of this scan
+        b.bucket_offsets = c.take<uint32_t>("bucket_offsets", t);         // inference too: the dev library's block plan weighs its blocks by differences of this scan
         b.tile_plan = c.take<uint32_t>("tile_plan", kPlanWords);
         if (training) {
             b.max_n_processed = c.take<uint32_t>("max_n_processed", t);

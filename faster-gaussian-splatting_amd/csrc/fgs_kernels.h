@@ -71,19 +71,19 @@ hipError_t launch_extract_ranges(int key_bytes, const void* sorted_keys, uint2* 
 #else
 #define FGS_SWITCH(name, value) constexpr int name = (value)
 #endif
-constexpr unsigned kPlannedBlocks = 254u;
+// K10's tile -> workgroup mappings (fgs_k10_mappings.h), the values of BlendArgs::row_group (0: the round-1 bands, 1..64: row groups, 255: the bands
+// bottom first). The product library always runs the first; the dev library selects among all of them (option 10).
 constexpr unsigned kColumnsTopDown = 252u, kColumnsBottomUp = 251u;   // one vertical strip of the image per XCD, walked row by row
+constexpr unsigned kPlannedBlocks = 254u;            // the device-side block plan (binning_exhibits.hip: plan_tiles_kernel)
 constexpr unsigned kBandsThroughPlan = 253u;         // A/B only: the round-1 bands, but with the plan's dependent load on every workgroup's path
-FGS_SWITCH(g_tile_row_group, static_cast<int>(kColumnsTopDown));   // blend_forward.hip: tile -> workgroup mapping (254: device-side block plan; 0: round-1 bands; 1..64 row groups)
 #ifdef FGS_DEV_SWITCHES
+FGS_SWITCH(g_tile_row_group, static_cast<int>(kColumnsTopDown));   // option 10: the mapping of the next forward pass (api.hip: bucket_scan_and_mapping)
+FGS_SWITCH(g_library_bucket_scan, 0);                // option 11: 1 = rocPRIM scan for K8+K9 and no tile plan (round-2 form, A/B)
+FGS_SWITCH(g_plan_experiment, 0);                    // binning_exhibits.hip, option 12: 1 = blocks unsorted and dealt statically (A/B of the deal itself)
 FGS_SWITCH(g_k11_chain_waves, 4096);                 // blend_backward_exhibits.hip, option 14: waves of the chained K11 exhibit (variant 5); 4096 = 16 resident waves x 256 CUs
 #endif
 FGS_SWITCH(g_seq_tiles, kSeqTiles);                  // preprocess.hip, option 5: PreprocessArgs::seq_tiles of every K1 launch
 FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
-#ifdef FGS_DEV_SWITCHES
-FGS_SWITCH(g_library_bucket_scan, 0);                // option 11: 1 = rocPRIM scan for K8+K9 and no tile plan (round-2 form, A/B)
-#endif
-FGS_SWITCH(g_plan_experiment, 0);                    // binning.hip, option 12: 1 = blocks unsorted and dealt statically (A/B of the deal itself)
 // radix_sort.hip: stable LSD radix sort of (key, uint32) pairs sized for these two sorts
 FGS_SWITCH(g_depth_sort_mode, 1);                    // option 9 -- bit 0: key range / 9-bit digits, bit 1: 2048-item workgroups (radix_sort.hip)
 size_t own_sort_temp_bytes(uint32_t n, int end_bit);
@@ -101,13 +101,16 @@ hipError_t own_sort_pairs_u32_device_count(void* temp, size_t temp_bytes, uint32
 hipError_t own_sort_pairs_u16_device_count(void* temp, size_t temp_bytes, uint16_t* keys[2], uint32_t* vals[2], int& selector, uint32_t capacity,
                                            const uint32_t* n_ptr, int end_bit, hipStream_t s);
 
-// K8+K9: inclusive scan of ceil(len/kBucket) per tile, and the tile -> workgroup plan of K10 (one single-workgroup kernel)
+// K8+K9: inclusive scan of ceil(len/kBucket) per tile (one single-workgroup kernel). tile_plan: nullptr -- always, in the product library -- or, dev
+// library, where the same launch also leaves K10's tile -> workgroup plan [kPlanWords] (binning_exhibits.hip)
 hipError_t launch_plan_tiles(const uint2* ranges, uint32_t* bucket_offsets, uint32_t* tile_plan, uint32_t n_tiles, uint32_t grid_w, uint32_t grid_h,
                              hipStream_t s);
-#ifdef FGS_DEV_SWITCHES
+#ifdef FGS_DEV_SWITCHES      // binning_exhibits.hip
+hipError_t launch_plan_tiles_exhibit(const uint2* ranges, uint32_t* bucket_offsets, uint32_t* tile_plan, uint32_t n_tiles, uint32_t grid_w, uint32_t grid_h,
+                                     hipStream_t s);      // the scan, then the plan (tile_plan != nullptr)
 size_t bucket_scan_temp_bytes(uint32_t n_tiles);      // the library scan, kept for A/B (fgs_debug_set_option(11, 1))
-#endif
 hipError_t run_bucket_scan(void* temp, size_t temp_bytes, const uint2* ranges, uint32_t* bucket_offsets, uint32_t n_tiles, hipStream_t s);
+#endif
 
 struct BlendArgs {                      // K10 / inference blend
     const uint2* ranges; const uint32_t* bucket_offsets; const uint32_t* inst_prims; const PrimRec* rec;
@@ -115,8 +118,10 @@ struct BlendArgs {                      // K10 / inference blend
     float* final_T; uint32_t* n_processed; uint32_t* max_n_processed;     // tile-major [T][192]
     uint32_t* bucket_tile; float4* ckpt;                                   // [B], [B][192]
     uint32_t width, height, grid_w, n_tiles;
-    uint32_t row_group;                      // tile -> workgroup mapping (blend_forward.hip: tile_of_workgroup); set by the launchers
-    const uint32_t* tile_plan;               // [kPlanWords] written by plan_tiles_kernel (row_group == kPlannedBlocks)
+    // row_group and tile_plan vary in the dev library alone (fgs_k10_mappings.h); the product library always passes kColumnsTopDown and no plan. One
+    // kernel-argument layout for both flavours.
+    uint32_t row_group;                      // tile -> workgroup mapping, set by the caller (api.hip: once per pass)
+    const uint32_t* tile_plan;               // [kPlanWords] written by plan_tiles_kernel; nullptr unless the mapping reads it (kPlannedBlocks, kBandsThroughPlan)
     uint32_t grid_h;
     int to_chw, clamp_output;
     float* scores;                        // pruning-score mode: accumulated per primitive [N]

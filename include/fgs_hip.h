@@ -421,7 +421,7 @@ int32_t fgs_debug_set_backward_variant(int32_t variant);
  * mapping: 252 (default) = one vertical strip of tile columns per XCD, walked row by row from the top (251: from the bottom), 0 = one
  * contiguous band of tile rows per XCD (rounds 1-2), g = 1..64 = groups of g rows dealt to the XCDs in turn, 255 = the bands walked
  * bottom-up, 254 = blocks of tiles weighed and dealt to the XCDs on the device (plan_tiles_kernel), 253 = the bands read through the plan
- * table (blend_forward.hip has the measurements), 11 = 1: rocPRIM scan for the per-tile bucket offsets (and no block plan), 12 = 1: the
+ * table (csrc/fgs_k10_mappings.h has the measurements; the product library always runs 252), 11 = 1: rocPRIM scan for the per-tile bucket offsets (and no block plan), 12 = 1: the
  * block plan without sorting (XCD x = block column x), 13 = upper bound of the grid of blend-backward variant 4.
  * Apart from key 7, results never depend on them. */
 int32_t fgs_debug_set_option(int32_t key, int32_t value);

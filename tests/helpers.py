@@ -419,13 +419,13 @@ def check_flip_aware(image, f_image, grads: dict, g_ref: dict, masks: dict, tol=
     return report
 
 
-# ---- K10's device-side tile plan (binning.hip: plan_tiles_kernel), restated in numpy for the tests ---------------------------------------------
+# ---- K10's device-side tile plan (binning_exhibits.hip: plan_tiles_kernel), restated in numpy for the tests ---------------------------------------------
 PLAN_BX, PLAN_BY, PLAN_HEADER = 8, 10, 4
 
 
 def planned_tile_of_workgroup(plan: np.ndarray, grid_w: int, grid_h: int) -> np.ndarray:
     """tile index blended by every workgroup of the planned K10 grid (-1 = padding workgroup), from the plan words the device wrote --
-    the same arithmetic as blend_forward.hip: tile_of_workgroup(row_group == kPlannedBlocks)."""
+    the same arithmetic as fgs_k10_mappings.h: tile_of_workgroup(row_group == kPlannedBlocks)."""
     bw, bh = -(-grid_w // PLAN_BX), -(-grid_h // PLAN_BY)
     assert (int(plan[0]), int(plan[1]), int(plan[2]), int(plan[3])) == (bw, bh, bw * bh, PLAN_BX * PLAN_BY // 8)
     per_block, per_xcd = bw * bh, PLAN_BX * PLAN_BY // 8

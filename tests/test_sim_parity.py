@@ -37,7 +37,7 @@ def _run(sim_backend, oracle, params, view, K=16, aa=False, bg=None, check_grads
 
 @pytest.mark.parametrize('w,h,n', [(333, 211, 300), (16, 12, 40)])
 def test_tile_plan_covers_every_tile_and_balances_the_xcds(sim_backend, w, h, n):
-    """K10's device-side tile -> workgroup plan (binning.hip: plan_tiles_kernel): whatever the image size and the distribution of the
+    """K10's device-side tile -> workgroup plan (binning_exhibits.hip: plan_tiles_kernel): whatever the image size and the distribution of the
     Gaussians, every tile is blended by exactly one workgroup, every XCD gets ten blocks in descending weight, and the greedy deal keeps
     the heaviest XCD within one block of the mean. Training and inference (which plans from the same scan)."""
     p, v = make_s0(seed=5, n=n)
@@ -57,7 +57,7 @@ def test_tile_plan_covers_every_tile_and_balances_the_xcds(sim_backend, w, h, n)
         lt = sim_backend.blob_layout(1, n, w, h, inf.state[1], inf.state[2])
         plan = sim_backend.view(inf.buffers[1], lt, 'tile_plan', torch.int32).numpy().view(np.uint32)
         assert np.array_equal(plan, dec['tile_plan'])
-        for m in (0, 251):                                                        # bands, columns bottom-up (252 = the default above; row groups: test_gpu)
+        for m in (0, 251):                                                        # bands, columns bottom-up (252 = the default above; every mapping, every entry point: test_k10_mappings.py)
             assert sim_backend.lib.fgs_debug_set_option(10, m) == 0
             assert torch.equal(sim_backend.forward(*[p[k] for k in helpers.NAMES], RS).image, ref.image), m
     finally:
