@@ -282,17 +282,20 @@ class Backend:
 
     def backward(self, densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings,
                  state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
-                 reached_blocks: Optional[torch.Tensor] = None) -> tuple:
+                 reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None) -> tuple:
         """`out`: optional six preallocated gradient tensors (e.g. views into one contiguous arena for a single RCCL call).
         `live_blocks`, `reached_blocks`: optional uint8 [ceil(N / 64)] on the device, filled with 1 / 0 per block of 64 Gaussians: some Gaussian of the
         block is visible / was reached by the backward blend pass. 0 = every gradient of the block is zero (still written) -- what
-        adam_step_multi(live_blocks=...) needs to skip reading those zeros; `reached_blocks` flags a superset of the zero blocks."""
+        adam_step_multi(live_blocks=...) needs to skip reading those zeros; `reached_blocks` flags a superset of the zero blocks.
+        `prior_blocks` (with `out` and `reached_blocks`): the same kind of array going IN -- 0 = the caller promises that the block's rows of all six
+        `out` tensors are zero already (the `reached_blocks` of the pass that last wrote them, untouched since); such a block is not written again
+        if this pass reaches none of its Gaussians (fgs_backward_recycled)."""
         return self.backward_aux(densification_info, grad_image, None, None, image, None, means, scales, rotations, opacities, sh_rest, buffers, settings,
-                                 state, out, live_blocks, reached_blocks)
+                                 state, out, live_blocks, reached_blocks, prior_blocks)
 
     def backward_aux(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
                      buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
-                     reached_blocks: Optional[torch.Tensor] = None) -> tuple:
+                     reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None) -> tuple:
         """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero). `depth` is the expected-depth
         map the forward pass returned (needed with grad_depth). Both None is `backward` exactly: no map is looked at, the scratch is `_scratch`'s and
         errors name fgs_backward; with a map gradient the scratch is `_scratch_aux`'s and errors name fgs_backward_aux."""
@@ -317,13 +320,14 @@ class Backend:
         dens = _densification(densification_info, n, device, validate=True)
         _check_block_flags('live_blocks', live_blocks, n, device)
         _check_block_flags('reached_blocks', reached_blocks, n, device)
+        _check_block_flags('prior_blocks', prior_blocks, n, device)
         scratch = (self._scratch_aux if aux else self._scratch)(n, settings, device)
         st = _lib.ForwardState(*state)
-        self._check(self.lib.fgs_backward_reached(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
-                                                  _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
-                                                  _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
-                                                  _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
-                                                  _stream_of(device)),
+        self._check(self.lib.fgs_backward_recycled(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
+                                                   _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
+                                                   _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
+                                                   _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+                                                   _ptr(prior_blocks), _stream_of(device)),
                     'fgs_backward_aux' if aux else 'fgs_backward')
         return grads
 

@@ -106,22 +106,87 @@ def live_block_stats() -> dict:
 
 
 def clear_live_blocks(owned=None) -> None:
-    """Forgets the registrations of the passes over the given parameter tensors (an optimizer's own), or all of them."""
+    """Forgets the registrations of the passes over the given parameter tensors (an optimizer's own), or all of them (and every spare arena)."""
     if owned is None:
         _LIVE['slots'].clear()
+        _RECYCLE['spares'].clear()
         return
     for t in owned:
-        _LIVE['slots'].pop(t.data_ptr(), None)
+        _retire(_LIVE['slots'].pop(t.data_ptr(), None))
 
 
-def _gradient_arena(shapes, device):
+def _gradient_arena(shapes, device, arena=None):
+    """One arena and the six gradient tensors as views into it; `arena`: a spare of exactly these shapes (the layout is a function of the shapes)."""
     numels = [math.prod(sh) for sh in shapes]
     offsets, total = [], 0
     for numel in numels:
         offsets.append(total)
         total += (numel + _ALIGN_FLOATS - 1) // _ALIGN_FLOATS * _ALIGN_FLOATS
-    arena = torch.empty(max(total, 1), dtype=torch.float32, device=device)
+    if arena is None:
+        arena = torch.empty(max(total, 1), dtype=torch.float32, device=device)
     return arena, tuple(arena[off:off + numel].view(sh) for sh, off, numel in zip(shapes, offsets, numels))
+
+
+# ---- the arena of the previous pass, used again -----------------------------------------------------------------------------------------
+# A new arena has to be written in full, 236 bytes per Gaussian, although in a dense scene all but a few per cent of its blocks get zeros that nobody
+# reads (the optimizer looks at the flags and at one sentinel float per block). The zeros only have to be written because the memory is new: in the arena
+# of the previous pass a block that was zero then and is unreached again is already correct. So an arena that leaves the registry above -- consumed by
+# match_live_blocks, or forgotten by clear_live_blocks(owned) -- is kept as a SPARE together with the version counter recorded for it and the
+# `reached_blocks` array its pass wrote, and the next backward pass over tensors of the same shapes on the same device writes into it, handing those flags
+# to the kernel as `prior_blocks` (fgs_backward_recycled): "0 = this block is zero now". The invariant is about the arena's content, not about whose
+# gradients it held, so spares are keyed by device and shapes: a second model of the same shapes may take the first one's.
+# A spare is used only if nobody can tell: its version counter is what was recorded (no torch-visible in-place edit since its pass: the accumulation of
+# a second backward, clipping, zero_grad(set_to_none=False)), and nobody else references its storage -- a `.grad` still alive, a kept alias of one
+# (`.detach()`, `.view(-1)`): a gradient somebody still holds never changes under them. The storage's reference count is compared with that of a newly
+# made tensor; the call that reads it is private torch API, and without it nothing is ever recycled. A write behind the version counter
+# (`.grad.data.add_(...)`) is the kernel's business, as it is for the optimizer: it looks at the first element of the block in each tensor and writes
+# the block unless all six are zero. Otherwise the pass takes new memory exactly as before, with no promise. Bit-identical results either way.
+# Cost: one arena stays allocated through the next forward pass (0.71 GB at 3 M Gaussians); set_gradient_recycling(False) gives it back.
+_RECYCLE = {'enabled': True, 'spares': {}, 'recycled': 0, 'fresh': 0, 'baseline': {}}
+_RECYCLE_MAX_SPARES = 2
+_STORAGE_USE_COUNT = getattr(torch._C, '_storage_Use_Count', None)
+
+
+def set_gradient_recycling(enabled: bool) -> None:
+    _RECYCLE['enabled'] = bool(enabled)
+    _RECYCLE['spares'].clear()
+
+
+def gradient_recycling_stats() -> dict:
+    """Backward passes of the hand-over path that wrote into the previous pass's arena / that took new memory."""
+    return {'recycled': _RECYCLE['recycled'], 'fresh': _RECYCLE['fresh']}
+
+
+def _storage_references(t: torch.Tensor) -> int:
+    return _STORAGE_USE_COUNT(t.untyped_storage()._cdata)
+
+
+def _retire(slot) -> None:
+    """A registration that leaves the registry: its arena becomes the spare of its device and shapes (one per key, the newest; a few overall)."""
+    if slot is None or not _RECYCLE['enabled'] or _STORAGE_USE_COUNT is None:
+        return
+    spares, arena = _RECYCLE['spares'], slot['arena']
+    key = (arena.device, tuple(shape for _, shape in slot['views']))
+    spares.pop(key, None)
+    spares[key] = {'arena': arena, 'version': slot['version'], 'flags': slot['flags']}
+    while len(spares) > _RECYCLE_MAX_SPARES:
+        del spares[next(iter(spares))]
+
+
+def _take_spare(shapes, device):
+    """The spare for these shapes if it may be written into (see above), else None; the spare leaves the table either way."""
+    spare = _RECYCLE['spares'].pop((device, tuple(tuple(sh) for sh in shapes)), None)
+    if spare is None or not _RECYCLE['enabled'] or _STORAGE_USE_COUNT is None:
+        return None
+    if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():      # a replayed pass would repeat a promise that was true once
+        return None
+    arena = spare['arena']
+    baseline = _RECYCLE['baseline'].get(device.type)
+    if baseline is None:
+        baseline = _RECYCLE['baseline'][device.type] = _storage_references(torch.empty(1, dtype=torch.float32, device=device))
+    if arena._version != spare['version'] or _storage_references(arena) != baseline:
+        return None
+    return spare
 
 
 def match_live_blocks(gradients, owned=None) -> 'torch.Tensor | None':
@@ -135,6 +200,7 @@ def match_live_blocks(gradients, owned=None) -> 'torch.Tensor | None':
     first = gradients[0].data_ptr()
     key = next((k for k in keys if any(address == first for address, _ in slots[k]['views'])), keys[0])
     slot = slots.pop(key)
+    _retire(slot)
     arena, flags, views, version = slot['arena'], slot['flags'], slot['views'], slot['version']
     by_address = {address: shape for address, shape in views if address != 0}
     seen = set()
@@ -313,14 +379,21 @@ class _Rasterize(torch.autograd.Function):
                 return (*zeros, None, None)
         n = means.shape[0]
         handover = _LIVE['enabled'] and _GRAD_OUT is None and n > 0
+        prior = None
         if handover:
-            arena, out = _gradient_arena(gradient_shapes(n, total_sh_rest(sh_rest)), means.device)
+            shapes = gradient_shapes(n, total_sh_rest(sh_rest))
+            spare = _take_spare(shapes, means.device)
+            if spare is not None:          # the previous pass's arena and what it says about its zeros; the flags of this pass go to a second array
+                prior = spare['flags']
+            _RECYCLE['recycled' if spare is not None else 'fresh'] += 1
+            arena, out = _gradient_arena(shapes, means.device, None if spare is None else spare['arena'])
+            del spare
             live, flags = torch.empty((2, (n + 63) // 64), dtype=torch.uint8, device=means.device)      # "any visible" / "any reached": the optimizer gets the latter
         else:
             clear_live_blocks([means])
             out, live, flags = (_GRAD_OUT() if _GRAD_OUT is not None else None), None, None
         grads = default_backend().backward(ctx.densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest,
-                                           buffers, ctx.rasterizer_settings, state, out=out, live_blocks=live, reached_blocks=flags)
+                                           buffers, ctx.rasterizer_settings, state, out=out, live_blocks=live, reached_blocks=flags, prior_blocks=prior)
         if handover:
             slots = _LIVE['slots']
             slots.pop(means.data_ptr(), None)

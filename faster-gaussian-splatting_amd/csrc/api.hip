@@ -404,6 +404,28 @@ int32_t fgs_backward_reached(const float* grad_image, const float* image, const 
                              float* densification_info, void* scratch,
                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                              uint8_t* reached_blocks, void* stream_) {
+    return fgs_backward_recycled(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                                 primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                                 grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                                 reached_blocks, nullptr, stream_);
+}
+
+// fgs_backward_reached for gradient tensors whose content the caller knows: prior_blocks[b] == 0 promises that block b of all six is zero NOW, and the
+// one-kernel K12 leaves such a block alone if it reaches none of its Gaussians (backward_gradients_kernel). The promise holds through the depth term as
+// well: launch_depth_mean_gradient adds to reached Gaussians only, and the reached test includes dL/dz.
+int32_t fgs_backward_recycled(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                              const float* means, const float* scales, const float* rotations, const float* opacities,
+                              const float* sh_coefficients_rest,
+                              void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                              float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                              float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                              float* densification_info, void* scratch,
+                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                              uint8_t* reached_blocks, const uint8_t* prior_blocks, void* stream_) {
+    if (prior_blocks != nullptr && reached_blocks == nullptr)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks without reached_blocks: the caller could not make the promise again for the next pass");
+    if (prior_blocks != nullptr && (prior_blocks == reached_blocks || prior_blocks == live_blocks))
+        return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks aliases %s: the pass reads the one while it writes the other", prior_blocks == reached_blocks ? "reached_blocks" : "live_blocks");
     const bool with_maps = grad_alpha != nullptr || grad_depth != nullptr;
     BackwardPlan P;
     if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state, with_maps)) return rc;
@@ -431,8 +453,9 @@ int32_t fgs_backward_reached(const float* grad_image, const float* image, const 
         StageScope t(ST_PREPROCESS_BACKWARD, stream);
         a.live_blocks = live_blocks;
         a.reached_blocks = reached_blocks;
+        a.prior_blocks = prior_blocks;
         FGS_HIP(launch_backward_gradients(a, sh, stream));
-    } else {
+    } else {                               // the two-kernel form writes every element and publishes all-ones flags: prior_blocks is not looked at
         if (live_blocks != nullptr) FGS_HIP(hipMemsetAsync(live_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // A/B form: no flags, every block "live"
         if (reached_blocks != nullptr) FGS_HIP(hipMemsetAsync(reached_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // ... and "reached"
         { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_preprocess_backward(false, a, stream)); }   // round-1 form: geometry kernel + SH-rest kernel

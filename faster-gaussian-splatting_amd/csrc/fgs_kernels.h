@@ -204,6 +204,10 @@ struct PreprocessBackwardArgs {         // K12, optionally fused with K13 for th
     // same form, same size, or nullptr -- 1 if K11 REACHED some Gaussian of the block (gaussian_backward's test, dL/dz of a depth-supervised pass included),
     // 0 if every row of the block is +-0 in all six gradient tensors: invisible blocks and the visible ones hidden behind opaque Gaussians
     uint8_t* reached_blocks;
+    // same form, same size, or nullptr -- the caller's promise going IN: 0 = every element of the block's rows compares equal to 0.0f in all six gradient
+    // tensors as they are now (e.g. the reached_blocks of the pass that last wrote these tensors); a wave that reaches no Gaussian then stores nothing,
+    // provided the block's first element of each tensor agrees (backward_gradients_kernel: block_promised_zero)
+    const uint8_t* prior_blocks;
     int vector_ok;                        // set by the launchers: every per-Gaussian tensor of the call is 16-byte aligned (coalesced 16-byte phase A)
 };
 hipError_t launch_preprocess_backward(bool fused_adam, const PreprocessBackwardArgs& a, hipStream_t s);

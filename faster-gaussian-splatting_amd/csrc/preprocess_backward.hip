@@ -480,18 +480,39 @@ fused_backward_adam_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) 
 #define FGS_K12_NT_STORES 1      // round 6: the 540 MB SH-rest gradient leaves as non-temporal stores (K12 0.248 -> 0.242 ms and the Adam kernel behind it
                                  // 0.771 -> 0.758 in alternating processes, profiles/r06_ab_k12_nt_stores.txt); 2: the 14 small floats as well (A/B)
 #endif
+// The caller's promise about what the gradient tensors hold NOW (PreprocessBackwardArgs::prior_blocks): block b of all six is zero already. A wave that
+// reaches no Gaussian would only write those zeros again -- nine tenths of this kernel's traffic in a dense scene -- so it may leave them alone. Belt and
+// braces as in adam_block_gradient_needed (adam.hip): the promise rests on the caller's proof that nobody touched the tensors since the pass that
+// published the flag, and a write behind the framework's bookkeeping (`.grad.data.add_(...)`, a raw pointer) is invisible to it. The block's first
+// element of every tensor -- six wave-uniform loads, requested at entry for a block flagged 0 -- must compare equal to 0.0f as well; anything else there (a whole-tensor edit such
+// as hand-written weight decay, NaN / Inf) and the block is written as before.
+__device__ __forceinline__ bool block_promised_zero(const PreprocessBackwardArgs& a, const ShRestArgs& sh, const WaveBlock& w) {
+    if (a.prior_blocks == nullptr) return false;
+    const size_t first = wave_uniform(w.first);
+    if (a.prior_blocks[first >> 6] != 0) return false;
+    const float s0 = a.grad_means[3u * first], s1 = a.grad_sh0[3u * first], s2 = a.grad_opacities[first], s3 = a.grad_scales[3u * first],
+                s4 = a.grad_rotations[4u * first], s5 = w.R > 0 ? sh.grad_sh_rest[first * w.R * 3u] : 0.0f;
+    return s0 == 0.0f && s1 == 0.0f && s2 == 0.0f && s3 == 0.0f && s4 == 0.0f && s5 == 0.0f;
+}
+
 template <int RT>
 __global__ void __launch_bounds__(256) backward_gradients_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) {
     __shared__ __attribute__((aligned(16))) float s_grad[256 / kWave][kWave * 15 * 3];
     const WaveBlock w = wave_block<RT>(a.n, sh.total_sh_rest);
     if (w.first >= a.n) return;
+    const bool promised_zero = block_promised_zero(a, sh, w);
     const uint32_t i = w.first + w.lane;
     const bool in_range = i < a.n;
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
     const float unused[14] = {};
     bool visible = false, reached = false;
+    if (in_range) visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol, reached);
+    float* const slice = s_grad[w.wv];
+    const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
+    if (a.live_blocks != nullptr && w.lane == 0) a.live_blocks[w.first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
+    if (a.reached_blocks != nullptr && w.lane == 0) a.reached_blocks[w.first >> 6] = any_reached ? 1 : 0;   // 0: every row of the block is +-0 in all six tensors
+    if (!any_reached && promised_zero) return;                         // the zeros are there already: none of the block's 59 x 64 floats is stored
     if (in_range) {
-        visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol, reached);
         // scalar stores at a stride of 4 w bytes: the write path combines them. Staging the wave's 64 x w block in LDS and storing it as one
         // coalesced 16-byte access per lane -- what pays in the fused kernel, where the same floats are also LOADED three times -- measured
         // 0.261 vs 0.252 ms here (profiles/archive/r02_ab_k12_coalesced_stores.txt)
@@ -507,10 +528,6 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
 #endif
             }
     }
-    float* const slice = s_grad[w.wv];
-    const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
-    if (a.live_blocks != nullptr && w.lane == 0) a.live_blocks[w.first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
-    if (a.reached_blocks != nullptr && w.lane == 0) a.reached_blocks[w.first >> 6] = any_reached ? 1 : 0;   // 0: all 59 floats of every row of the block were written as +0
     if (w.R == 0) return;
     if (any_reached) {                                                 // a wave K11 reached no Gaussian of writes its SH-rest block as zeros
         float B[15];

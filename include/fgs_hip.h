@@ -143,6 +143,28 @@ int32_t fgs_backward_reached(const float* grad_image, const float* image, const 
                              float* densification_info, void* scratch,
                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                              uint8_t* reached_blocks, void* stream);
+/* fgs_backward_reached for gradient tensors whose content the caller knows -- the tensors of an earlier pass used again instead of new memory.
+ * prior_blocks: [ceil(n_primitives / 64)] device bytes, read only. prior_blocks[b] == 0 is the CALLER'S PROMISE that every element of rows
+ * 64 b .. 64 b + 63 of all six gradient tensors compares equal to 0.0f now, when the pass starts (+0 or -0) -- e.g. the reached_blocks output of the pass
+ * that last wrote these very tensors, if nothing has written to them since. 1 promises nothing. A block with prior_blocks[b] == 0 that this pass
+ * reaches no Gaussian of is then NOT WRITTEN: its zeros are there already (the 236 bytes per Gaussian of such blocks are nine tenths of the traffic
+ * of this stage in a dense scene). The result is what fgs_backward_reached leaves, bit for bit except that a -0 of such a block stays -0. As a guard
+ * the kernel also looks at the block's FIRST element in each of the six tensors and writes the block after all unless all six compare equal to 0.0f:
+ * a whole-tensor edit the caller's bookkeeping missed (hand-written weight decay, NaN) is caught; a foreign write that leaves those six elements zero
+ * is not -- then the promise was false and the stale values stay. Every other block is written in full as before (a reached block including the
+ * zeros of its unreached rows); live_blocks, reached_blocks and densification_info are written as before in every case.
+ * NULL prior_blocks is fgs_backward_reached exactly. FGS_ERR_INVALID_ARGUMENT, before anything is launched: prior_blocks without reached_blocks (the
+ * caller could not continue the chain), prior_blocks aliasing reached_blocks or live_blocks (ping-pong between two arrays). Map gradients are accepted:
+ * the depth term is added to reached Gaussians only. */
+int32_t fgs_backward_recycled(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                              const float* means, const float* scales, const float* rotations, const float* opacities,
+                              const float* sh_coefficients_rest,
+                              void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                              float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                              float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                              float* densification_info, void* scratch,
+                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                              uint8_t* reached_blocks, const uint8_t* prior_blocks, void* stream);
 
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
