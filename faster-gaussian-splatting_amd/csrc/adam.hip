@@ -6,13 +6,10 @@
 namespace fgs {
 
 // ---- K13: Adam for all parameter groups in one launch (adam.cu:10-34), float4-vectorised, U pieces per thread ----------
-// g_adam_unroll = 1: 16-byte pieces per thread (fgs_debug_set_option(1, u)); measured on MI355X: 1, 2 and 4 are within 2 %
-// g_adam_reverse = 1 (fgs_debug_set_option(8, 0|1) in the dev build): reversed workgroup order (measured 0.837 vs 0.855 ms at S2, tools/ab_adam_order.py)
-// g_adam_nontemporal = 1 (fgs_debug_set_option(2, 0|1) in the dev build): non-temporal loads / stores (state is streamed once per step: +2.3 % measured)
-// (round 6, measured and withdrawn: the updated PARAMETERS alone as ordinary stores, on the idea that the next forward pass reads them first -- K1 0.227 vs 0.201 ms,
-// Adam 0.797 vs 0.782: dirty lines in eight L2s are the last thing the next kernel's reads want to meet, profiles/r06_ab_adam_param_nt.txt)
+// The product runs one form: one 16-byte piece per thread, non-temporal, workgroups in reverse order. The forms it was measured against are the dev
+// library's launch_adam_exhibit, in front of the launcher at the end of this file.
 
-// NT: non-temporal access (the state is streamed once per step); only adam_kernel<.., false> asks for ordinary loads and stores
+// NT: non-temporal access (the state is streamed once per step); only adam_kernel<.., false>, an exhibit, asks for ordinary loads and stores
 template <bool NT> __device__ __forceinline__ float4 load4(const float* p) { return NT ? load_float4_nt(p) : *reinterpret_cast<const float4*>(p); }
 template <bool NT> __device__ __forceinline__ void store4(float* p, const float4 v) {
     if (NT) store_float4_nt(p, v);
@@ -136,21 +133,45 @@ hipError_t launch_adam_quiet_scan(const AdamQuietScanArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_adam(const AdamArgs& a_in, hipStream_t s) {
-    AdamArgs a = a_in;
-    const int unroll_opt = g_adam_unroll, nontemporal = g_adam_nontemporal;
-    const int u = nontemporal ? 1 : (unroll_opt == 2 || unroll_opt == 4 ? unroll_opt : 1);
-    uint32_t blocks = 0;                                  // first_block / total_blocks depend on the elements per workgroup
+// first_block of every group and total_blocks, for workgroups of 256 threads x u 16-byte pieces; returns total_blocks
+static uint32_t assign_adam_blocks(AdamArgs& a, const int u) {
+    uint32_t blocks = 0;
     for (int k = 0; k < a.n_groups; ++k) { a.g[k].first_block = blocks; blocks += static_cast<uint32_t>((a.g[k].n + 1024 * u - 1) / (1024 * u)); }
-    a.total_blocks = blocks;
-    a.reverse = g_adam_reverse;
-    if (blocks == 0) return hipSuccess;
-#ifdef FGS_DEV_SWITCHES                                    // the product's switches are constants: it carries adam_kernel<1, true> and nothing else
-    if (!nontemporal && u == 1) hipLaunchKernelGGL((adam_kernel<1, false>), dim3(blocks), dim3(256), 0, s, a);
-    else if (!nontemporal && u == 2) hipLaunchKernelGGL((adam_kernel<2, false>), dim3(blocks), dim3(256), 0, s, a);
-    else if (!nontemporal) hipLaunchKernelGGL((adam_kernel<4, false>), dim3(blocks), dim3(256), 0, s, a);
-    else
+    return a.total_blocks = blocks;
+}
+
+#ifdef FGS_DEV_SWITCHES
+// ---- the dev library's A/B exhibits of K13 (libfgs_hip_dev.so only; the product carries adam_kernel<1, true> and nothing else) ----
+// g_adam_unroll = 1: 16-byte pieces per thread (fgs_debug_set_option(1, u)); measured on MI355X: 1, 2 and 4 are within 2 %
+// g_adam_reverse = 1 (fgs_debug_set_option(8, 0|1) in the dev build): reversed workgroup order (measured 0.837 vs 0.855 ms at S2, tools/ab_adam_order.py)
+// g_adam_nontemporal = 1 (fgs_debug_set_option(2, 0|1) in the dev build): non-temporal loads / stores (state is streamed once per step: +2.3 % measured)
+// (round 6, measured and withdrawn: the updated PARAMETERS alone as ordinary stores, on the idea that the next forward pass reads them first -- K1 0.227 vs 0.201 ms,
+// Adam 0.797 vs 0.782: dirty lines in eight L2s are the last thing the next kernel's reads want to meet, profiles/r06_ab_adam_param_nt.txt)
+// false: the switches select the product's form and nothing was enqueued
+static bool launch_adam_exhibit(const AdamArgs& a_in, hipStream_t s) {
+    const int unroll_opt = g_adam_unroll, nontemporal = g_adam_nontemporal, reverse = g_adam_reverse;
+    if (nontemporal && reverse) return false;
+    AdamArgs a = a_in;
+    a.reverse = reverse;
+    const int u = nontemporal ? 1 : (unroll_opt == 2 || unroll_opt == 4 ? unroll_opt : 1);      // unroll applies to the plain-load kernels only
+    const uint32_t blocks = assign_adam_blocks(a, u);
+    if (blocks == 0) return true;
+    if (nontemporal) hipLaunchKernelGGL((adam_kernel<1, true>), dim3(blocks), dim3(256), 0, s, a);
+    else if (u == 1) hipLaunchKernelGGL((adam_kernel<1, false>), dim3(blocks), dim3(256), 0, s, a);
+    else if (u == 2) hipLaunchKernelGGL((adam_kernel<2, false>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((adam_kernel<4, false>), dim3(blocks), dim3(256), 0, s, a);
+    return true;
+}
 #endif
+
+hipError_t launch_adam(const AdamArgs& a_in, hipStream_t s) {
+#ifdef FGS_DEV_SWITCHES
+    if (launch_adam_exhibit(a_in, s)) return hipGetLastError();
+#endif
+    AdamArgs a = a_in;
+    a.reverse = 1;
+    const uint32_t blocks = assign_adam_blocks(a, 1);
+    if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL((adam_kernel<1, true>), dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -111,7 +111,7 @@ int32_t fgs_shard_preprocess(const float* means, const float* scales, const floa
             PreprocessArgs& pa = pb.v[k];
             params.write(pa);
             pa.rec = b.rec; pa.n_touched = b.n_touched; pa.depth_keys = b.keys[0]; pa.prim_idx = b.prims[0]; pa.counters = b.counters; pa.huge_list = b.offsets; pa.hot_list = b.hot_list; pa.foot = nullptr;
-            pa.count_appended = 1; pa.seq_tiles = g_seq_tiles;
+            pa.count_appended = 1;
             pa.n = n; pa.cam = camera_of(settings[v], geo); pa.ranges = nullptr; pa.n_tiles = 0;   // the tile ranges belong to the renderer of the view
             // slot table for fgs_shard_backward: the second depth-key buffer is free on this path (no sort on the owner)
             rb.v[k] = PackRecordsView{b.rec, b.n_touched, b.keys[0], b.prims[0], b.counters, b.keys[1],

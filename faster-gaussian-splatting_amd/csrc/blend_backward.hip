@@ -93,11 +93,6 @@ __global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const Backwar
     }
 }
 
-#ifdef FGS_DEV_SWITCHES
-#define FGS_ABLATE(a) ((a).ablate)      // timing experiments of the dev build (fgs_debug_set_option key 7)
-#else
-#define FGS_ABLATE(a) 0
-#endif
 // ---- variant 3 (default): work list of live buckets + compacted live pixels + two-value pipeline state -----------------
 // The formulation this library ships; the four it was measured against -- variants 0 / 2 (the file header's systolic form over ALL buckets and all 192
 // pixels), 1, 4 and 5 -- are exhibits of the dev library in a unit of their own, blend_backward_exhibits.hip.
@@ -449,7 +444,6 @@ __global__ void __launch_bounds__(256) depth_mean_gradient_kernel(const float* _
 
 #ifdef FGS_DEV_SWITCHES
 __global__ void mark_accumulators_dirty_kernel(uint32_t* flag) { *flag = 1u; }      // the A/B variants that do not end in the fold kernel
-std::atomic<int> g_backward_ablate{0};    // fgs_debug_set_option(7, bits): timing experiments only -- 1: no atomics, 2: no step loop (results are wrong)
 std::atomic<int> g_backward_variant{3};   // 3 (default): work list + compacted pixels + two-value state; 2: systolic over all buckets / all 192 pixels, dL/dC from
                               // global memory (round 1: 0.70 ms at S2); 0: same with dL/dC in LDS (0.74); 1: strip (lane = pixel, 0.85 ms);
                               // 4: lane = pixel on the matrix cores; 5: chained -- all but 3 in blend_backward_exhibits.hip; fgs_debug_set_backward_variant()

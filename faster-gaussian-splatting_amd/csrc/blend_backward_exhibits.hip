@@ -860,6 +860,7 @@ extern "C" __attribute__((visibility("default"))) int fgs_debug_k11m_phases(unsi
 namespace fgs {
 #endif
 
+std::atomic<int> g_backward_ablate{0};    // fgs_debug_set_option(7, bits): timing experiments only -- 1: no atomics, 2: no step loop (results are wrong)
 std::atomic<int> g_k11m_max_blocks{FGS_K11M_MAX_BLOCKS};   // variant 4: upper bound of its grid (fgs_debug_set_option(13, n)); items beyond it are walked grid-stride
 
 // The exhibit kernel of a.variant (anything but 3), and nothing else: launch_blend_backward (blend_backward.hip) follows it with the kernel that

@@ -24,6 +24,13 @@
 #define FGS_K11_IF_STATS(...)
 #endif
 
+// option 7 of the dev library (g_backward_ablate, blend_backward_exhibits.hip): timing experiments that switch parts of the kernels off
+#ifdef FGS_DEV_SWITCHES
+#define FGS_ABLATE(a) ((a).ablate)      // timing experiments of the dev build (fgs_debug_set_option key 7)
+#else
+#define FGS_ABLATE(a) 0
+#endif
+
 // the top of a work item (the timestamp counter runs at 100 MHz, the same clock on every CU; the cycle counter is not)
 #define FGS_K11_PROBE_ITEM_BEGIN() \
     FGS_K11_IF_TIMELINE(const unsigned long long t_start_ = __builtin_amdgcn_s_memrealtime(); \

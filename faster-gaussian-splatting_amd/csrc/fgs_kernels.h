@@ -23,7 +23,7 @@ struct PreprocessArgs {                 // K1
     uint2* ranges; uint32_t n_tiles;               // cleared by the kernel (K0)
     float* acc;                                    // training: K11's accumulator records [N][9]; K1 clears those of the Gaussians it finds visible (else nullptr)
     uint32_t n;
-    int seq_tiles;                                 // candidate tiles each lane tests itself before the wave cooperates (1..32)
+    int seq_tiles;                                 // dev library: candidate tiles each lane tests itself before the wave cooperates (1..32, fgs_k1_exhibits.h); 0 = the flattened count
     int count_appended;                            // sharded path: counters[2] counts the huge-footprint entries appended to the list
     CameraArgs cam;
 };
@@ -63,9 +63,10 @@ hipError_t run_tile_sort(void* temp, size_t temp_bytes, int key_bytes, void* key
                          uint32_t n_instances, const uint32_t* n_instances_ptr, int end_bit, hipStream_t s);
 hipError_t launch_extract_ranges(int key_bytes, const void* sorted_keys, uint2* ranges, uint32_t n_instances, const uint32_t* n_instances_ptr, hipStream_t s);
 
-// A/B switches. In the product library every one of them is a compile-time constant (its adopted value): nothing process-wide can change what a
-// launch does. libfgs_hip_dev.so (-DFGS_DEV_SWITCHES) makes them process-wide atomics behind fgs_debug_set_option for the A/B tools; atomics make a
-// concurrent set / launch well defined (a launch sees the old or the new value, never a torn one).
+// A/B switches. libfgs_hip_dev.so (-DFGS_DEV_SWITCHES) has them as process-wide atomics behind fgs_debug_set_option (api_debug.hip, the one switchboard)
+// for the A/B tools; atomics make a concurrent set / launch well defined (a launch sees the old or the new value, never a torn one). The product library
+// has none of them -- nothing process-wide can change what a launch does -- but for the one its host code still reads, g_fused_single_kernel, which is a
+// compile-time constant there (its adopted value). Each switch names the dev-only file that holds its other arms.
 #ifdef FGS_DEV_SWITCHES
 #define FGS_SWITCH(name, value) inline std::atomic<int> name{value}
 #else
@@ -81,11 +82,14 @@ FGS_SWITCH(g_tile_row_group, static_cast<int>(kColumnsTopDown));   // option 10:
 FGS_SWITCH(g_library_bucket_scan, 0);                // option 11: 1 = rocPRIM scan for K8+K9 and no tile plan (round-2 form, A/B)
 FGS_SWITCH(g_plan_experiment, 0);                    // binning_exhibits.hip, option 12: 1 = blocks unsorted and dealt statically (A/B of the deal itself)
 FGS_SWITCH(g_k11_chain_waves, 4096);                 // blend_backward_exhibits.hip, option 14: waves of the chained K11 exhibit (variant 5); 4096 = 16 resident waves x 256 CUs
+FGS_SWITCH(g_seq_tiles, kSeqTiles);                  // fgs_k1_exhibits.h, option 5: PreprocessArgs::seq_tiles of every K1 launch (0: the product's flattened count)
+FGS_SWITCH(g_depth_sort_mode, 1);                    // sort_exhibits.hip, option 9 -- bit 0: key range / 9-bit digits, bit 1: 2048-item workgroups; 1 = the product's sort
+FGS_SWITCH(g_adam_reverse, 1);                       // adam.hip (launch_adam_exhibit), option 8: reversed workgroup order
+FGS_SWITCH(g_adam_nontemporal, 1);                   // same, option 2: non-temporal loads / stores
+FGS_SWITCH(g_adam_unroll, 1);                        // same, option 1: 1, 2 or 4 float4 pieces per thread (plain loads / stores only)
 #endif
-FGS_SWITCH(g_seq_tiles, kSeqTiles);                  // preprocess.hip, option 5: PreprocessArgs::seq_tiles of every K1 launch
 FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
 // radix_sort.hip: stable LSD radix sort of (key, uint32) pairs sized for these two sorts
-FGS_SWITCH(g_depth_sort_mode, 1);                    // option 9 -- bit 0: key range / 9-bit digits, bit 1: 2048-item workgroups (radix_sort.hip)
 size_t own_sort_temp_bytes(uint32_t n, int end_bit);
 // Side table carried out of the depth sort's LAST scatter pass (radix_sort.hip): the sort's values start as the input positions (the first pass
 // makes them up), the last pass gathers rows_in[value] and writes the row, its first word as the sorted value, and the row's tile count in sorted order.
@@ -93,6 +97,10 @@ struct SortPayload { const uint4* rows_in; uint4* rows_out; uint32_t* count_out;
                      uint32_t* big_list; uint32_t* big_count; };      // depth-order positions of the rows whose boxes exceed kBigInstanceFootprint candidates
 hipError_t own_depth_sort(void* temp, size_t temp_bytes, uint32_t* keys[2], uint32_t* vals[2], int& selector, uint32_t n, const uint32_t* n_ptr,
                           DepthKeyRange range, hipStream_t s, const SortPayload* payload = nullptr);
+#ifdef FGS_DEV_SWITCHES      // sort_exhibits.hip: the depth sort under option 9 != 1 (true: it ran, `result` is its error code)
+bool depth_sort_exhibit(hipError_t& result, void* temp, size_t temp_bytes, uint32_t* keys[2], uint32_t* vals[2], int& selector, uint32_t n,
+                        const uint32_t* n_ptr, DepthKeyRange range, hipStream_t s, const SortPayload* payload);
+#endif
 hipError_t own_sort_pairs_u32(void* temp, size_t temp_bytes, uint32_t* keys[2], uint32_t* vals[2], int& selector, uint32_t n, int end_bit, hipStream_t s);
 hipError_t own_sort_pairs_u16(void* temp, size_t temp_bytes, uint16_t* keys[2], uint32_t* vals[2], int& selector, uint32_t n, int end_bit, hipStream_t s);
 // the item count lives on the device (*n_ptr <= capacity): lets the depth sort start before the host has read the counters back
@@ -301,11 +309,8 @@ hipError_t launch_gather_rows(const GatherArgs& a, hipStream_t s);
 size_t morton_temp_bytes(uint32_t n);
 hipError_t run_morton_order(const float* means, const float* lo, const float* hi, int64_t* order_out, uint32_t n, void* temp, size_t temp_bytes, hipStream_t s);
 
-FGS_SWITCH(g_adam_reverse, 1);                                               // option 8: reversed workgroup order (adam.hip)
-FGS_SWITCH(g_adam_nontemporal, 1);                                           // option 2: non-temporal loads / stores
-FGS_SWITCH(g_adam_unroll, 1);                                                // option 1: 1, 2 or 4 float4 pieces per thread
 #ifdef FGS_DEV_SWITCHES
-extern std::atomic<int> g_backward_ablate;
+extern std::atomic<int> g_backward_ablate;                                   // blend_backward_exhibits.hip, option 7 (FGS_ABLATE: fgs_k11_probes.h)
 extern std::atomic<int> g_k11m_max_blocks;                                   // blend_backward_exhibits.hip
 extern std::atomic<int> g_backward_variant;                                  // 3 compact (default, blend_backward.hip); 0 / 2 systolic, 1 strip, 4 lane = pixel, 5 chained (blend_backward_exhibits.hip)
 // the exhibit kernel of a.variant != 3 alone (blend_backward_exhibits.hip); launch_blend_backward adds the fold / dirty-mark kernel behind it and reads the error

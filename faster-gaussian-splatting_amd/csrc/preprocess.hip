@@ -9,6 +9,8 @@
 // Built with -ffp-contract=off: screen bounds / tile counts / depth keys are bit-reproducible against the oracle.
 #include "fgs_kernels.h"
 #include <fgs_wave.h>
+#include "fgs_k1_probes.h"
+#include "fgs_k1_exhibits.h"
 
 namespace fgs {
 
@@ -17,28 +19,8 @@ namespace fgs {
 __device__ __forceinline__ int float_to_int_floor(float x) { return static_cast<int>(floorf(fminf(fmaxf(x, -1.0e9f), 1.0e9f))); }
 __device__ __forceinline__ int float_to_int_ceil(float x) { return static_cast<int>(ceilf(fminf(fmaxf(x, -1.0e9f), 1.0e9f))); }
 
-// Debug-only phase timer (tools/k1_phase_timer.sh builds a separate library with -DFGS_K1_PHASE_TIMER; the product build has none of it):
-// every wave keeps the cycles it spent between two marks in (scalar) registers and stores them ONCE, to its own slot of g_k1_phase, at the
-// end -- a first version with one atomic per mark onto eight shared words slowed the kernel 9x and measured only itself. A wave's memory
-// waits land in the phase that first uses the data, i.e. where the wave stalls. Result at S2 (profiles/archive/r02_k1_phases.txt): loads +
-// projection 20 %, flattened tile count 26 %, SH colour + record 23 %, and 24 % in the last phase -- waves waiting at the workgroup
-// barrier of the compaction for slower siblings, not the counter's round trip: requesting the counter before the colour phase so that
-// the round trip overlaps with it made the kernel 6.5 % SLOWER (profiles/archive/r02_ab_k1_early_counter.txt) and was reverted.
-#ifdef FGS_K1_PHASE_TIMER
-constexpr unsigned kK1TimerWaves = 1u << 17;
-__device__ unsigned long long g_k1_phase[kK1TimerWaves * 8];
-#define FGS_K1_MARK(i) do { const unsigned long long now_ = __builtin_readcyclecounter(); t_phase_[i] += now_ - t_prev_; t_prev_ = now_; } while (0)
-#define FGS_K1_START unsigned long long t_phase_[8] = {}; unsigned long long t_prev_ = __builtin_readcyclecounter()
-#define FGS_K1_FLUSH do { const unsigned w_ = (blockIdx.x * kPreprocessBlock + threadIdx.x) >> 6; \
-                          if (lane_id() < 8u && w_ < kK1TimerWaves) g_k1_phase[w_ * 8u + lane_id()] += t_phase_[0] * (lane_id() == 0) + t_phase_[1] * (lane_id() == 1) + \
-                              t_phase_[2] * (lane_id() == 2) + t_phase_[3] * (lane_id() == 3) + t_phase_[4] * (lane_id() == 4) + t_phase_[5] * (lane_id() == 5); } while (0)
-#else
-#define FGS_K1_MARK(i) do { } while (0)
-#define FGS_K1_START do { } while (0)
-#define FGS_K1_FLUSH do { } while (0)
-#endif
-
-template <bool INFERENCE>
+// SEQUENTIAL: the dev library's A/B exhibit of the count of small footprints (fgs_k1_exhibits.h); the product instantiates the flattened count alone
+template <bool INFERENCE, bool SEQUENTIAL = false>
 __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a) {
     FGS_K1_START;
     const Camera cam = load_camera(a.cam);
@@ -112,17 +94,9 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a) {
             if (huge) active = false;
             const TileTest tt = make_tile_test(m2x - 0.5f, m2y - 0.5f, ca, cb, cc, power_threshold);
             uint64_t hit_mask = 0;          // bit t = candidate tile t (row-major in the tile bounding box) is overlapped; t < 64
-            unsigned first_shared = 0;      // candidates below this index were handled by one of the first two schemes
-            if (a.seq_tiles > 0) {
-                // (A/B reference, fgs_debug_set_option(5, n)) the reference's scheme: every lane tests the first n candidates of its
-                // own Gaussian (cfg:54: 4), the wave cooperates on the rest. At a mean footprint of 9 candidates a wave runs all n
-                // rounds with half of its lanes idle.
-                first_shared = static_cast<unsigned>(a.seq_tiles);
-                if (active) {
-                    const unsigned n_seq = n_max < first_shared ? n_max : first_shared;
-                    for (unsigned t = 0; t < n_seq; ++t)
-                        if (tile_contributes(tt, tx0 + t % tbw, ty0 + t / tbw)) { ++cnt; hit_mask |= 1ull << t; }
-                }
+            unsigned first_shared;          // candidates below this index were handled by one of the first two schemes
+            if constexpr (SEQUENTIAL) {
+                first_shared = count_tiles_sequential(a.seq_tiles, active, tt, tx0, ty0, tbw, n_max, cnt, hit_mask);
             } else {
                 // Flattened: the (Gaussian, candidate) pairs of all footprints of <= 64 candidates are laid end to end (prefix sum of
                 // the counts) and the wave takes 64 PAIRS per round, every lane busy: lane l of round r handles pair 64 r + l, finds its
@@ -184,7 +158,7 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a) {
                 ot.pt = wave_read(tt.pt, src);
                 ot.den_x = wave_read(tt.den_x, src); ot.den_y = wave_read(tt.den_y, src);
                 ot.rcp_x = wave_read(tt.rcp_x, src); ot.rcp_y = wave_read(tt.rcp_y, src);
-                const unsigned first = a.seq_tiles > 0 ? first_shared : 0u;
+                const unsigned first = SEQUENTIAL ? first_shared : 0u;      // the flattened count leaves these footprints whole
                 unsigned found = 0;
                 for (unsigned base = first; base < o_cnt; base += kWave) {
                     const unsigned t = base + lane;
@@ -217,27 +191,7 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a) {
             }
             if (visible || huge) {
                 float col[3];
-#if defined(FGS_K1_SH_PROBE)
-                // TIMING PROBE, wrong colours (tools/build_variant.sh k1probe preprocess.hip -DFGS_K1_SH_PROBE): the lane's 45 coefficients are taken from the
-                // wave's 11.25 KB block with perfectly coalesced 16-byte loads (lane l takes float4 i*64 + l of the block) -- what staging the block through LDS
-                // could reach at most, without the LDS traffic. Measured: 0.198-0.201 -> 0.188-0.189 ms (profiles/r06_ab_k1_sh_probe.txt): the staging was not built.
-                float kk[48];
-                {
-                    const size_t wave_first = (size_t)(idx & ~63u) * 45u;
-                    const size_t total = (size_t)a.n * 45u;
-                    const float* blk = a.sh_rest + wave_first;
-#pragma unroll
-                    for (int i = 0; i < 12; ++i) {
-                        const size_t e = ((size_t)i * 64u + lane) * 4u;
-                        const bool in = i < 11 ? (wave_first + e + 3u < total) : (lane < 16u && wave_first + e + 3u < total);
-                        const float4 v = in ? *reinterpret_cast<const float4*>(blk + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        kk[4 * i] = v.x; kk[4 * i + 1] = v.y; kk[4 * i + 2] = v.z; kk[4 * i + 3] = v.w;
-                    }
-                }
-                const float* k = kk;
-#else
-                const float* k = a.sh_rest + (size_t)idx * cam.total_sh_rest * 3;
-#endif
+                FGS_K1_SH_COEFFICIENTS(k, a, cam, idx, lane);
                 sh_to_color(a.sh0 + 3 * (size_t)idx, k, m[0] - cam.pos[0], m[1] - cam.pos[1], m[2] - cam.pos[2],
                             (unsigned)cam.active_sh_bases, col);
                 if (INFERENCE) { col[0] = fmaxf(col[0], 0.0f); col[1] = fmaxf(col[1], 0.0f); col[2] = fmaxf(col[2], 0.0f); }  // ki:200
@@ -319,6 +273,24 @@ __device__ __forceinline__ void preprocess_body(const PreprocessArgs& a) {
 template <bool INFERENCE>
 __global__ void FGS_K1_BOUNDS preprocess_kernel(const PreprocessArgs a) { preprocess_body<INFERENCE>(a); }
 __global__ void __launch_bounds__(kPreprocessBlock) preprocess_batch_kernel(const PreprocessBatch b) { preprocess_body<false>(b.v[blockIdx.y]); }
+#ifdef FGS_DEV_SWITCHES      // option 5 != 0: the same kernels around the sequential count (fgs_k1_exhibits.h), enqueued in place of the three above
+template <bool INFERENCE>
+__global__ void FGS_K1_BOUNDS preprocess_sequential_kernel(const PreprocessArgs a) { preprocess_body<INFERENCE, true>(a); }
+__global__ void __launch_bounds__(kPreprocessBlock) preprocess_sequential_batch_kernel(const PreprocessBatch b) { preprocess_body<false, true>(b.v[blockIdx.y]); }
+static bool launch_preprocess_sequential(bool inference, PreprocessArgs a, dim3 grid, hipStream_t s) {      // false: the switch selects the flattened count
+    if ((a.seq_tiles = g_seq_tiles) <= 0) return false;
+    if (inference) hipLaunchKernelGGL(preprocess_sequential_kernel<true>, grid, dim3(kPreprocessBlock), 0, s, a);
+    else hipLaunchKernelGGL(preprocess_sequential_kernel<false>, grid, dim3(kPreprocessBlock), 0, s, a);
+    return true;
+}
+static bool launch_preprocess_sequential_batch(PreprocessBatch b, dim3 grid, hipStream_t s) {
+    const int seq_tiles = g_seq_tiles;
+    if (seq_tiles <= 0) return false;
+    for (int v = 0; v < b.n_views; ++v) b.v[v].seq_tiles = seq_tiles;
+    hipLaunchKernelGGL(preprocess_sequential_batch_kernel, grid, dim3(kPreprocessBlock), 0, s, b);
+    return true;
+}
+#endif
 
 // Exact tile count + compaction for the few screen-filling footprints: one kHugeBlock-thread workgroup per Gaussian, kHugeBlock candidate
 // tiles per step (kernel_utils.cuh:117-180 with the whole workgroup cooperating instead of one warp). 1024 threads (round 5; 256 before): the
@@ -369,6 +341,10 @@ __global__ void __launch_bounds__(kHugeBlock) preprocess_huge_batch_kernel(const
 hipError_t launch_preprocess(bool inference, const PreprocessArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     const dim3 grid((a.n + kPreprocessBlock - 1) / kPreprocessBlock), block(kPreprocessBlock);
+#ifdef FGS_DEV_SWITCHES
+    if (launch_preprocess_sequential(inference, a, grid, s)) { }
+    else
+#endif
     if (inference) hipLaunchKernelGGL(preprocess_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(preprocess_kernel<false>, grid, block, 0, s, a);
     hipLaunchKernelGGL(preprocess_huge_kernel, dim3(a.n < 512u ? a.n : 512u), dim3(kHugeBlock), 0, s, a);
@@ -379,29 +355,12 @@ hipError_t launch_preprocess_batch(const PreprocessBatch& b, hipStream_t s) {
     const uint32_t n = b.v[0].n;
     if (n == 0 || b.n_views <= 0) return hipSuccess;
     const dim3 grid((n + kPreprocessBlock - 1) / kPreprocessBlock, static_cast<unsigned>(b.n_views)), block(kPreprocessBlock);
+#ifdef FGS_DEV_SWITCHES
+    if (!launch_preprocess_sequential_batch(b, grid, s))
+#endif
     hipLaunchKernelGGL(preprocess_batch_kernel, grid, block, 0, s, b);
     hipLaunchKernelGGL(preprocess_huge_batch_kernel, dim3(n < 256u ? n : 256u, static_cast<unsigned>(b.n_views)), dim3(kHugeBlock), 0, s, b);
     return hipGetLastError();
 }
 
 }  // namespace fgs
-
-#ifdef FGS_K1_PHASE_TIMER
-// debug build only: sum (and optionally clear) the per-wave, per-phase cycle counts of preprocess_body
-extern "C" __attribute__((visibility("default"))) int fgs_debug_k1_phases(unsigned long long* out8, int reset) {
-    static unsigned long long host[fgs::kK1TimerWaves * 8];
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(fgs::g_k1_phase), sizeof(host)) != hipSuccess) return -1;
-    for (int i = 0; i < 8; ++i) out8[i] = 0;
-    for (unsigned w = 0; w < fgs::kK1TimerWaves; ++w) for (int i = 0; i < 8; ++i) out8[i] += host[w * 8u + i];
-    if (reset) {
-        void* dev = nullptr;
-        if (hipGetSymbolAddress(&dev, HIP_SYMBOL(fgs::g_k1_phase)) != hipSuccess || hipMemset(dev, 0, sizeof(host)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-// the raw per-wave table ([wave][8] cycles, waves in launch order): for the distribution of a phase over the waves (is the kernel's time a tail?)
-extern "C" __attribute__((visibility("default"))) int fgs_debug_k1_phase_waves(unsigned long long* out, unsigned n_waves) {
-    if (n_waves > fgs::kK1TimerWaves) n_waves = fgs::kK1TimerWaves;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(fgs::g_k1_phase), sizeof(unsigned long long) * 8u * n_waves) == hipSuccess ? 0 : -1;
-}
-#endif

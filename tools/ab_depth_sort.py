@@ -1,4 +1,4 @@
-"""A/B of the depth-sort variants inside one process (fgs_debug_set_option(9, m)): 0 = round 1 (4 x 8 bits over all 32 bits, 4096-item
+"""A/B of the depth-sort variants inside one process (dev library: fgs_debug_set_option(9, m), csrc/sort_exhibits.hip; 1 is the product's sort): 0 = round 1 (4 x 8 bits over all 32 bits, 4096-item
 workgroups), 1 = key - bits(near) in 9-bit passes (27 bits = 3 passes for near 0.2 / far 1e4), 2 = 2048-item workgroups, 3 = both; 1 is the default.
 Stage time of the depth sort and the whole frame, 8 views of S2, three rounds."""
 import sys, torch

@@ -1,4 +1,5 @@
-"""A/B of K1's sequential-tile threshold inside one process (stage times from HIP events, all 8 views of S2)."""
+"""A/B of K1's tile-counting schemes inside one process (dev library: fgs_debug_set_option(5, n) -- 0 = the flattened count of every library, n > 0 = the
+sequential exhibit of csrc/fgs_k1_exhibits.h with n candidates per lane; stage times from HIP events, all 8 views of S2)."""
 import sys, torch
 sys.path[:0] = ['/root/repo', '/root/repo/faster-gaussian-splatting_amd']
 import bench

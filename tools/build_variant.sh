@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds faster-gaussian-splatting_amd/libfgs_hip_<name>.so: the current objects with ONE source recompiled with extra flags (A/B and ablation builds).
 # usage: bash tools/build_variant.sh <name> <source.hip> <flags...>       e.g.  bash tools/build_variant.sh k5ab1 binning.hip -DFGS_K5_ABLATE=1
+#        K1's SH timing probe (csrc/fgs_k1_probes.h):                        bash tools/build_variant.sh k1probe preprocess.hip -DFGS_K1_SH_PROBE
 set -e
 cd "$(dirname "$0")/../faster-gaussian-splatting_amd/csrc"
 name=$1; src=$2; shift 2

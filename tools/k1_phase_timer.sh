@@ -1,6 +1,6 @@
 #!/bin/bash
 # Where does K1 (preprocess) spend its time? Builds a SEPARATE library with cycle-counter probes between the phases of preprocess_body
-# (-DFGS_K1_PHASE_TIMER, csrc/preprocess.hip) -- the product library is untouched -- and prints each phase's share of the wave-cycles.
+# (-DFGS_K1_PHASE_TIMER, csrc/fgs_k1_probes.h) -- the product library is untouched -- and prints each phase's share of the wave-cycles.
 # usage: bash tools/k1_phase_timer.sh build   (here: cross-compiles)      bash tools/k1_phase_timer.sh run   (on the GPU box)
 set -e
 R=${GRAFT_REPO_ROOT:-/root/repo}; C=$R/faster-gaussian-splatting_amd/csrc; LIB=$R/faster-gaussian-splatting_amd/libfgs_hip_k1timer.so
