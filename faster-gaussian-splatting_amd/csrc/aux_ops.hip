@@ -37,7 +37,9 @@ __global__ void __launch_bounds__(256) relocation_kernel(const float* __restrict
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float old_opacity = old_opacities[i];
-    const int n_samples = min(max(static_cast<int>(n_samples_per_primitive[i]), 1), kMcmcMaxSamples);
+    // clamped as the 64-bit count it is: the reference narrows to int first (kernels_mcmc.cuh:41), which turns 2^40 + 7 draws into 7
+    const int64_t n_drawn = n_samples_per_primitive[i];
+    const int n_samples = n_drawn < 1 ? 1 : n_drawn > kMcmcMaxSamples ? kMcmcMaxSamples : static_cast<int>(n_drawn);
     const float new_opacity = 1.0f - powf(1.0f - old_opacity, 1.0f / static_cast<float>(n_samples));
     new_opacities[i] = new_opacity;
     float denominator = 0.0f;

@@ -242,10 +242,12 @@ def _split_mass(g: Gaussians, sources: torch.Tensor, min_opacity: float, relocat
     the opacity / scale that keeps the rendered result (Model.py:382-391 / 424-433 semantics). Returns (opacity logits [k, 1], log scales [k, 3])
     for the `sources` list, the same value for every occurrence of a source."""
     multiplicity = torch.bincount(sources, minlength=g.means.shape[0])[sources] + 1
-    activated = torch.sigmoid(g.opacities.detach()).flatten()[sources].reshape(-1, 1).contiguous()
+    ceiling = 1.0 - torch.finfo(torch.float32).eps
+    # below 1: a logit of 17.3 or more is exactly 1.0 after the fp32 sigmoid, where Eq. 9's alternating sum cancels to nothing and the factor of a source drawn
+    # some 20 times or more is wrong or negative (NaN log-scales). The reference's Model.py:385-391 passes the activated opacity as it is and shares this.
+    activated = torch.sigmoid(g.opacities.detach()).flatten()[sources].reshape(-1, 1).clamp(max=ceiling).contiguous()
     extents = g.scales.detach()[sources].exp().contiguous()
     shared_opacity, shared_extent = relocation_adjustment(activated, extents, multiplicity)
-    ceiling = 1.0 - torch.finfo(torch.float32).eps
     return shared_opacity.clamp(min_opacity, ceiling).logit().reshape(-1, 1), shared_extent.log()
 
 

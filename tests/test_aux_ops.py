@@ -63,3 +63,45 @@ def test_gpu_aux_ops_match_numpy_restatement(hip_backend, oracle):
     assert not torch.equal(before, means)
     o, s = B.relocation_adjustment(torch.full((4, 1), 0.5).cuda(), torch.ones(4, 3).cuda(), torch.tensor([1, 2, 3, 4]).cuda())
     assert torch.allclose(o[0], torch.tensor(0.5, device='cuda')) and o.shape == (4, 1) and s.shape == (4, 3)
+
+
+# ---- the same three operators against high-precision models at their edges (tests/aux_op_cases.py; on hardware: tests/test_gpu_aux_ops.py) ----
+import aux_op_cases as cases  # noqa: E402
+
+
+@pytest.mark.parametrize('n', cases.ROW_COUNTS)
+def test_sim_aux_ops_row_counts_and_guard_rows(sim_backend, oracle, n):
+    cases.check_row_counts(sim_backend, oracle, 'cpu', n)
+
+
+def test_sim_relocation_matches_decimal_model(sim_backend, oracle):
+    cases.check_relocation_against_model(sim_backend, oracle, 'cpu')
+
+
+def test_sim_relocation_clamp_and_dtypes(sim_backend, oracle):
+    cases.check_relocation_clamp_and_dtypes(sim_backend, oracle, 'cpu')
+
+
+def test_sim_relocation_saturated_opacity_small_counts(sim_backend, oracle):
+    cases.check_relocation_saturated_opacity(sim_backend, oracle, 'cpu')
+
+
+def test_sim_add_noise_matches_fp64_model(sim_backend, oracle):
+    cases.check_add_noise_against_model(sim_backend, oracle, 'cpu')
+
+
+def test_sim_add_noise_thresholds_and_opaque_rows(sim_backend, oracle):
+    cases.check_add_noise_thresholds(sim_backend, oracle, 'cpu')
+
+
+@pytest.mark.parametrize('principal_point', cases.EXACT_PRINCIPAL_POINTS, ids=('centred', 'off-centre'))
+def test_sim_3d_filter_exact_boundaries(sim_backend, oracle, principal_point):
+    cases.check_filter_exact_boundaries(sim_backend, oracle, 'cpu', principal_point)
+
+
+def test_sim_3d_filter_two_views_leave_the_minimum(sim_backend, oracle):
+    cases.check_filter_two_views(sim_backend, oracle, 'cpu')
+
+
+def test_sim_3d_filter_random_scene_matches_fp64_model(sim_backend, oracle):
+    cases.check_filter_random_scene(sim_backend, oracle, 'cpu')

@@ -1,5 +1,6 @@
 """Adaptive density control / pruning / sorting with Adam-state surgery (reference Model.py:262-366).
 CPU tests of the tensor semantics; the GPU end-to-end run is tests/test_gpu_training.py."""
+import functools
 import math
 
 import numpy as np
@@ -174,6 +175,25 @@ def test_mcmc_densification_relocates_and_grows():
     assert D.mcmc_densification(g, 0.005, 208, generator=torch.Generator().manual_seed(2), ops=_sim_ops())['added'] == 0
 
 
+def test_mcmc_densification_survives_a_saturated_source():
+    """A source whose logit has reached 20 has an activated opacity of exactly 1.0 in fp32. Eq. 9's alternating sum then cancels from terms of 1e10 and more
+    and the kernel's factor (the reference's arithmetic) turns wrong and then negative as the count grows; the logarithm of the shared scale was NaN.
+    _split_mass keeps the opacity it hands over below 1, at the ceiling it applies to the result anyway."""
+    g = _gaussians(45)
+    with torch.no_grad():
+        g.opacities[:] = -12.0                   # everything dead ...
+        g.opacities[0] = 20.0                    # ... but one saturated source
+        g.opacities[1:3] = -5.0                  # and two faint ones (sigmoid 0.0067 > min_opacity) that are hardly ever drawn
+    assert float(torch.sigmoid(g.opacities.detach()[0])) == 1.0
+    source_mean = g.means.detach()[0].clone()
+    stats = D.mcmc_densification(g, 0.005, 45, generator=torch.Generator().manual_seed(0), ops=_sim_ops())
+    assert stats['relocated'] == 42 and stats['added'] == 0           # the 42 dead rows, whatever the generator draws; the cap leaves no growth
+    copies = int((g.means.detach() == source_mean).all(dim=1).sum())
+    assert copies >= 31, copies                  # drawn at least 30 of 42 times: each draw picks it with probability 0.987, whatever the stream
+    assert torch.isfinite(g.opacities.detach()).all() and torch.isfinite(g.scales.detach()).all()
+    assert float(torch.sigmoid(g.opacities.detach()).min()) >= 0.005 - 1e-6
+
+
 def test_importance_pruning_and_noise_hook():
     g = _gaussians(100)
     scores = torch.arange(100, dtype=torch.float32)
@@ -288,6 +308,139 @@ def test_device_gather_and_morton_order(sim_backend, oracle):
     outs = sim_backend.gather_rows(tensors, idx)
     for t, o in zip(tensors, outs):
         assert torch.equal(o, t[idx])
+
+
+# ---- morton_order / gather_rows at the sort's workgroup edges, under ties and on degenerate boxes (on hardware: tests/test_gpu_densify.py) ----
+GUARD_ROWS, SENTINEL = 64, -7777
+MORTON_COUNTS = (0, 1, 2, 255, 256, 257, 1000, 4095, 4096, 4097, 8193)       # the keys' 256-lane workgroups; the sort's 4096-item ones
+
+
+def _near_integer_coordinates(k: int):
+    """float32 m in [0, 1] whose scaled value fl(m * 1023) is k itself, and the closest the product comes to k from below and from above (one or two float32
+    steps: the product moves in steps of 1023 ulp(m))."""
+    f = np.float32
+    around = [f(k / 1023.0)]
+    for _ in range(8):
+        around = [np.nextafter(around[0], f(0))] + around + [np.nextafter(around[-1], f(2))]
+    scaled = [f(c * f(1023.0)) for c in around]
+    on = [c for c, t in zip(around, scaled) if t == f(k)]
+    below = max(c for c, t in zip(around, scaled) if t < f(k))
+    above = min(c for c, t in zip(around, scaled) if t > f(k))
+    assert on and 0 < f(k) - f(below * f(1023.0)) <= 2 * np.spacing(f(k)) and 0 < f(above * f(1023.0)) - f(k) <= 2 * np.spacing(f(k)), k
+    return on[0], below, above           # the cell-k point first: rounding instead of truncating ties it with the one below, in index order
+
+
+@functools.lru_cache(maxsize=None)
+def morton_points(name):
+    rng = np.random.default_rng(99)
+    f = np.float32
+    if isinstance(name, int):
+        pts = rng.uniform(-3.0, 3.0, (name, 3)) * [1.0, 2.0, 0.5]
+    elif name in ('ties_8', 'ties_300'):
+        distinct = rng.uniform(-3.0, 3.0, (int(name.split('_')[1]), 3))
+        pts = distinct[rng.integers(0, distinct.shape[0], 8193)]
+    elif name == 'identical':
+        pts = np.tile([[0.3, -1.2, 4.0]], (1000, 1))                                  # hi == lo on every axis: the 1e-12 clamp of the span
+    elif name == 'flat_axis':
+        pts = rng.uniform(-3.0, 3.0, (1000, 3))
+        pts[:, 1] = 0.75
+    elif name == 'lo_and_hi':                                                         # cells 0, 1022 and 1023 of every axis, the last cell listed first
+        pts = np.array([np.where(np.arange(3) == axis, v, 0.0) for axis in range(3) for v in (1.0, 1022.5 / 1023.0, 0.0)])
+    elif name == 'near_integers':
+        rows = [(0.0, 0.0, 0.0), (1.0, 1.0, 1.0)]
+        for k in (1, 2, 511, 512, 1000, 1022):
+            for m in _near_integer_coordinates(k):
+                rows += [(m, 0.5, 0.5), (0.5, 0.5, m)]
+        pts = np.array(rows)
+    elif name == 'axis_significance':                                                 # x over y over z: the order is origin, z, y, x
+        pts = np.array([(1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, 0.0)])
+    out = np.ascontiguousarray(pts, f).reshape(-1, 3)
+    out.setflags(write=False)
+    return out
+
+
+MORTON_SHAPES = ('ties_8', 'ties_300', 'identical', 'flat_axis', 'lo_and_hi', 'near_integers', 'axis_significance')
+
+
+def _morton_order_into_guarded_output(be, means):
+    """fgs_morton_order as Backend.morton_order calls it, into an order tensor with GUARD_ROWS sentinel rows behind it. Mirrors the call sequence of
+    FasterGSCudaBackend/_backend.py: Backend.morton_order (box on the device, fgs_morton_order_temp_bytes, one call) -- keep the two in step; the caller
+    compares this result with the wrapper's, so a protocol that drifts apart shows as a failure here, not as a silently stale test."""
+    _, _backend = helpers.backend_modules()
+    n, device = means.shape[0], means.device
+    whole = torch.full((n + GUARD_ROWS,), SENTINEL, dtype=torch.int64, device=device)
+    if n > 0:
+        lo, hi = means.min(dim=0).values.contiguous(), means.max(dim=0).values.contiguous()
+        nbytes = int(be.lib.fgs_morton_order_temp_bytes(n))
+        temp = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        be._check(be.lib.fgs_morton_order(means.data_ptr(), lo.data_ptr(), hi.data_ptr(), whole.data_ptr(), n, temp.data_ptr(), nbytes, _backend._stream_of(device)), 'fgs_morton_order')
+    assert torch.equal(whole[n:].cpu(), torch.full((GUARD_ROWS,), SENTINEL, dtype=torch.int64)), 'morton_order wrote behind row N'
+    return whole[:n]
+
+
+def check_morton_order(be, oracle, device, name):
+    pts = morton_points(name)
+    means = torch.from_numpy(pts.copy()).to(device)
+    order = be.morton_order(means)
+    assert order.dtype == torch.int64 and order.shape == (pts.shape[0],)
+    expected = oracle.morton_order(pts) if pts.shape[0] else np.zeros(0, np.int64)
+    assert np.array_equal(order.cpu().numpy(), expected), name
+    assert torch.equal(_morton_order_into_guarded_output(be, means), order)
+    got = order.cpu().numpy()
+    if name in ('ties_8', 'ties_300', 'identical'):                # stable: equal points (hence equal keys) keep their index order
+        _, group = np.unique(pts, axis=0, return_inverse=True)
+        group = group.reshape(-1)[got]
+        for k in range(int(group.max()) + 1):
+            assert np.all(np.diff(got[group == k]) > 0), (name, k)
+        assert len(np.unique(group)) == {'ties_8': 8, 'ties_300': 300, 'identical': 1}[name]
+    if name == 'axis_significance':
+        assert got.tolist() == [3, 2, 1, 0]
+    if name == 'lo_and_hi':                                          # per axis: cell 0, then 1022, then 1023
+        for axis in range(3):
+            where = [int(np.nonzero(got == 3 * axis + j)[0][0]) for j in (2, 1, 0)]
+            assert where == sorted(where), (axis, where)
+
+
+def check_gather_rows(be, device):
+    gen = torch.Generator().manual_seed(8)
+    n = 300
+    shapes = [(3,), (1, 3), (15, 3), (1,), (3,), (4,), (3,), (1, 3), (0, 3), (1,), (3,), (4,), (3,), (1, 3), (15, 3), (1,), (3,), (4,), (3,)]
+    assert len(shapes) == 19 and shapes[8] == (0, 3)              # a width-0 tensor in the middle; the 19th takes the second launch of the 18-tensor chunking
+    tensors = [torch.randn((n,) + sh, generator=gen).to(device) for sh in shapes]
+    indices = {'repeats': torch.randint(0, n, (517,), generator=gen), 'reversed': torch.arange(n - 1, -1, -1), 'empty': torch.zeros(0, dtype=torch.int64),
+               'one row': torch.tensor([n - 1]), 'int32': torch.randint(0, n, (257,), generator=gen).to(torch.int32)}
+    _, _backend = helpers.backend_modules()
+    for name, index in indices.items():
+        index = index.to(device)
+        outs = be.gather_rows(tensors, index)
+        assert len(outs) == 19
+        for t, o in zip(tensors, outs):
+            assert o.shape == (index.shape[0],) + tuple(t.shape[1:]) and torch.equal(o, t[index.long()]), name
+        # the same launches into outputs with guard rows behind them: the call sequence of FasterGSCudaBackend/_backend.py: Backend.gather_rows (chunks of 18,
+        # widths = floats per row, int64 index) -- keep the two in step
+        rows, idx64 = index.shape[0], index.long().contiguous()
+        wholes = [torch.full((rows + GUARD_ROWS,) + tuple(t.shape[1:]), float(SENTINEL), device=device) for t in tensors]
+        for first in range(0, 19, 18):
+            chunk, oc = tensors[first:first + 18], [w[:rows] for w in wholes[first:first + 18]]
+            widths = [int(t.numel() // t.shape[0]) for t in chunk]
+            be._check(be.lib.fgs_gather_rows(len(chunk), _backend._pointer_array(chunk, len(chunk)), _backend._pointer_array(oc, len(chunk)),
+                                             (_backend.C.c_int32 * len(chunk))(*widths), _backend._ptr(idx64), rows, _backend._stream_of(idx64.device)), 'fgs_gather_rows')
+        for t, w in zip(tensors, wholes):
+            assert torch.equal(w[:rows], t[idx64]) and bool((w[rows:] == float(SENTINEL)).all()), name
+    # a tensor of zero rows beside non-empty ones: only the empty index can address it
+    beside = [torch.zeros((0, 3), device=device), tensors[0], torch.zeros((0, 15, 3), device=device), tensors[2]]
+    for t, o in zip(beside, be.gather_rows(beside, indices['empty'].to(device))):
+        assert o.shape == (0,) + tuple(t.shape[1:]) and torch.equal(o, t[indices['empty'].to(device)])
+    assert be.gather_rows([], indices['reversed'].to(device)) == []
+
+
+@pytest.mark.parametrize('name', MORTON_COUNTS + MORTON_SHAPES)
+def test_device_morton_order_edges_ties_and_degenerate_boxes(sim_backend, oracle, name):
+    check_morton_order(sim_backend, oracle, 'cpu', name)
+
+
+def test_device_gather_rows_index_and_tensor_edges(sim_backend):
+    check_gather_rows(sim_backend, 'cpu')
 
 
 def test_harness_densify_uses_the_device_passes(sim_backend, oracle):

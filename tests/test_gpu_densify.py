@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import helpers  # noqa: F401
-from test_densify import ORDER, _adc_case, check_adc_against_restatement
+from test_densify import MORTON_COUNTS, MORTON_SHAPES, ORDER, _adc_case, check_adc_against_restatement, check_gather_rows, check_morton_order
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -30,6 +30,16 @@ def test_gather_rows_and_morton_order_on_device(hip_backend, oracle):
     keep = torch.nonzero(torch.rand(200_001, device=DEV) > 0.3).flatten()
     for t, o in zip(tensors, hip_backend.gather_rows(tensors, keep)):
         assert torch.equal(o, t[keep])
+
+
+@pytest.mark.parametrize('name', MORTON_COUNTS + MORTON_SHAPES)
+def test_morton_order_edges_ties_and_degenerate_boxes_on_device(hip_backend, oracle, name):
+    """The 200 001 random points above have almost no equal keys; here 8 193 points share 8 (then 300) keys, boxes collapse and counts straddle the sort's 4096."""
+    check_morton_order(hip_backend, oracle, DEV, name)
+
+
+def test_gather_rows_index_and_tensor_edges_on_device(hip_backend):
+    check_gather_rows(hip_backend, DEV)
 
 
 def test_training_with_device_densification(hip_backend):
