@@ -280,6 +280,9 @@ class Backend:
     def _scratch_aux(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
         return _empty_bytes(self.lib.fgs_backward_aux_scratch_bytes(n, int(settings.width), int(settings.height)), device)
 
+    def _scratch_pose(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
+        return _empty_bytes(self.lib.fgs_backward_pose_scratch_bytes(n, int(settings.width), int(settings.height)), device)
+
     def backward(self, densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings,
                  state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
                  reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None) -> tuple:
@@ -299,7 +302,26 @@ class Backend:
         """`backward` with upstream gradients of the maps of `forward_aux`: grad_alpha / grad_depth [H,W] or None (= zero). `depth` is the expected-depth
         map the forward pass returned (needed with grad_depth). Both None is `backward` exactly: no map is looked at, the scratch is `_scratch`'s and
         errors name fgs_backward; with a map gradient the scratch is `_scratch_aux`'s and errors name fgs_backward_aux."""
+        return self._backward(densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest, buffers,
+                              settings, state, out, live_blocks, reached_blocks, prior_blocks)[:6]
+
+    def backward_pose(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
+                      buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
+                      reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None,
+                      w2c: bool = True, cam_position: bool = True) -> tuple:
+        """`backward_aux` that also returns the gradient of the camera of `settings` (fgs_backward_pose): the six gradients, then grad_w2c [3,4] (rows
+        0..2 of w2c; w2c and cam_position are independent inputs) and grad_cam_position [3] -- None for one that was not asked for. Neither asked for
+        is `backward_aux` exactly. Map gradients may be None."""
+        return self._backward(densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest, buffers,
+                              settings, state, out, live_blocks, reached_blocks, prior_blocks, (w2c, cam_position))
+
+    def _backward(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
+                  buffers, settings, state, out, live_blocks, reached_blocks, prior_blocks, camera: 'tuple | None' = None) -> tuple:
+        """The materialised-gradient backward pass behind backward / backward_aux (camera=None: fgs_backward_recycled) and backward_pose
+        (camera = which of (grad_w2c, grad_cam_position) are wanted: fgs_backward_pose): the six gradients + (grad_w2c, grad_cam_position)."""
         aux = grad_alpha is not None or grad_depth is not None
+        want_w2c, want_cam = camera if camera is not None else (False, False)
+        pose = want_w2c or want_cam
         device = self._check_params((means, scales, rotations, opacities, sh_rest), BACKWARD_PARAMETER_NAMES)
         keep: list = []
         n = means.shape[0]
@@ -321,15 +343,19 @@ class Backend:
         _check_block_flags('live_blocks', live_blocks, n, device)
         _check_block_flags('reached_blocks', reached_blocks, n, device)
         _check_block_flags('prior_blocks', prior_blocks, n, device)
-        scratch = (self._scratch_aux if aux else self._scratch)(n, settings, device)
+        scratch = (self._scratch_pose if pose else self._scratch_aux if aux else self._scratch)(n, settings, device)
         st = _lib.ForwardState(*state)
-        self._check(self.lib.fgs_backward_recycled(_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
-                                                   _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
-                                                   _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
-                                                   _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
-                                                   _ptr(prior_blocks), _stream_of(device)),
-                    'fgs_backward_aux' if aux else 'fgs_backward')
-        return grads
+        args = (_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
+                _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
+                _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
+                _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks), _ptr(prior_blocks))
+        if camera is None:
+            self._check(self.lib.fgs_backward_recycled(*args, _stream_of(device)), 'fgs_backward_aux' if aux else 'fgs_backward')
+            return grads + (None, None)
+        grad_w2c = torch.empty((3, 4), dtype=torch.float32, device=device) if want_w2c else None
+        grad_cam = torch.empty(3, dtype=torch.float32, device=device) if want_cam else None
+        self._check(self.lib.fgs_backward_pose(*args, _ptr(grad_w2c), _ptr(grad_cam), _stream_of(device)), 'fgs_backward_pose')
+        return grads + (grad_w2c, grad_cam)
 
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
                             buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,

@@ -463,6 +463,83 @@ def diff_rasterize_aux(means: torch.Tensor, scales: torch.Tensor, rotations: tor
     return image, (a if alpha else None), (d if depth else None)
 
 
+class _RasterizePose(torch.autograd.Function):
+    """_RasterizeAux whose camera is an input: w2c ([3,4] or [4,4]) and cam_position ([3]) replace the tensors of the settings and receive gradients
+    (fgs_backward_pose). The maps are optional: without them the forward pass is the plain one. Always synchronous, gradients in fresh tensors."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, w2c, cam_position,
+                rasterizer_settings: RasterizerSettings, alpha: bool, depth: bool):
+        _require_gpu(means)
+        settings = rasterizer_settings._replace(w2c=w2c.detach(), cam_position=cam_position.detach())
+        params = (means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest)
+        be = default_backend()
+        if alpha or depth:
+            res = be.forward_aux(*params, settings, alpha, depth)
+            res_alpha, res_depth = res.alpha, res.depth
+        else:
+            res = be.forward(*params, settings)
+            res_alpha = res_depth = None
+        ctx.rasterizer_settings = settings
+        ctx.buffer_state = res.state
+        ctx.has_depth = res_depth is not None
+        ctx.camera = (tuple(w2c.shape), w2c.dtype, cam_position.dtype)
+        ctx.set_materialize_grads(False)
+        shape = (settings.height, settings.width)
+        a = res_alpha if res_alpha is not None else means.new_empty(shape)
+        d = res_depth if res_depth is not None else means.new_empty(shape)
+        ctx.save_for_backward(res.image, d, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.mark_non_differentiable(densification_info, *([a] if res_alpha is None else []), *([d] if res_depth is None else []))
+        return res.image, a, d
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_alpha, grad_depth):
+        image, depth, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        if not ctx.has_depth:
+            grad_depth = None
+        clear_live_blocks([means])
+        # a camera input that does not require grad costs nothing: neither asked for is backward_aux exactly, the POSE kernel is not launched
+        *grads, grad_w2c, grad_cam = default_backend().backward_pose(
+            ctx.densification_info, grad_image.contiguous(), grad_alpha.contiguous() if grad_alpha is not None else None,
+            grad_depth.contiguous() if grad_depth is not None else None, image, depth, means, scales, rotations, opacities, sh_rest, buffers,
+            ctx.rasterizer_settings, ctx.buffer_state, w2c=ctx.needs_input_grad[7], cam_position=ctx.needs_input_grad[8])
+        w2c_shape, w2c_dtype, cam_dtype = ctx.camera
+        if grad_w2c is not None:
+            if w2c_shape[0] == 4:                 # the last row of a [4,4] w2c is not read
+                grad_w2c = torch.cat([grad_w2c, grad_w2c.new_zeros((1, 4))])
+            grad_w2c = grad_w2c.to(w2c_dtype)
+        if grad_cam is not None:
+            grad_cam = grad_cam.to(cam_dtype)
+        return (*grads, None, grad_w2c, grad_cam, None, None, None)
+
+
+def diff_rasterize_pose(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                        sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                        rasterizer_settings: RasterizerSettings, w2c: 'torch.Tensor | None' = None, cam_position: 'torch.Tensor | None' = None,
+                        alpha: bool = False, depth: bool = False):
+    """Training render that is also differentiable in the camera pose: (image [3,H,W], alpha [H,W] or None, depth [H,W] or None), the maps as in
+    diff_rasterize_aux. `w2c` ([4,4] or [3,4]) and `cam_position` ([3]) override the tensors of the settings (None: the settings' own) and may
+    require grad; they are independent inputs, as in the settings. With cam_position=None and a w2c that requires grad the position is derived
+    here as -w2c[:3,:3].T @ w2c[:3,3], so autograd composes both gradients into w2c's. The gradient of a [4,4] w2c has a zero last row. A camera
+    input that does not require grad costs nothing. No gradient for the intrinsics."""
+    w2c_given = w2c is not None
+    if not w2c_given:
+        w2c = rasterizer_settings.w2c
+    if w2c.dim() != 2 or tuple(w2c.shape) not in ((3, 4), (4, 4)):
+        raise ValueError(f'diff_rasterize_pose: w2c must be [4,4] or [3,4], not {tuple(w2c.shape)}')
+    if cam_position is None:
+        cam_position = -w2c[:3, :3].T @ w2c[:3, 3] if w2c_given else rasterizer_settings.cam_position
+    if cam_position.numel() != 3:
+        raise ValueError(f'diff_rasterize_pose: cam_position must have 3 entries, not {tuple(cam_position.shape)}')
+    image, a, d = _RasterizePose.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                                       w2c, cam_position.reshape(3), rasterizer_settings, bool(alpha), bool(depth))
+    return image, (a if alpha else None), (d if depth else None)
+
+
 def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
               sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
               to_chw: bool, clamp_output: bool = True) -> torch.Tensor:

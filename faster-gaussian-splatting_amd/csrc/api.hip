@@ -422,6 +422,33 @@ int32_t fgs_backward_recycled(const float* grad_image, const float* image, const
                               float* densification_info, void* scratch,
                               int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                               uint8_t* reached_blocks, const uint8_t* prior_blocks, void* stream_) {
+    return fgs_backward_pose(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                             primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                             grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                             reached_blocks, prior_blocks, nullptr, nullptr, stream_);
+}
+
+size_t fgs_backward_pose_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height) {
+    if (n_primitives < 0 || width <= 0 || height <= 0) return 0;
+    Carver c(nullptr);
+    BackwardScratch::carve(c, static_cast<uint32_t>(n_primitives), geometry_of(width, height).n_tiles, true);
+    PoseScratch::carve(c, static_cast<uint32_t>(n_primitives));
+    return c.total();
+}
+
+// fgs_backward_recycled that also reduces, inside K12, what the per-Gaussian chains say about the camera: dL/dw2c (rows 0..2) and dL/dcam_position.
+// Both outputs NULL: the pass is fgs_backward_recycled's, kernel for kernel, on the plain (or aux) scratch layout. Otherwise the scratch has the aux
+// layout -- whether or not map gradients arrive: the plain layout is its prefix -- with the pose partials behind it.
+int32_t fgs_backward_pose(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                          const float* means, const float* scales, const float* rotations, const float* opacities,
+                          const float* sh_coefficients_rest,
+                          void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                          float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                          float* densification_info, void* scratch,
+                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                          uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream_) {
+    const bool with_pose = grad_w2c != nullptr || grad_cam_position != nullptr;
     if (prior_blocks != nullptr && reached_blocks == nullptr)
         return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks without reached_blocks: the caller could not make the promise again for the next pass");
     if (prior_blocks != nullptr && (prior_blocks == reached_blocks || prior_blocks == live_blocks))
@@ -433,10 +460,15 @@ int32_t fgs_backward_recycled(const float* grad_image, const float* image, const
     if (grad_depth && !(state->selector & kStateDepthCheckpoints))
         return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth needs the depth checkpoints that fgs_forward_aux writes: these buffers were filled by a forward pass without them");
     if (grad_depth && !depth_expected) return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth without depth_expected (the map fgs_forward_aux returned)");
-    if (n_primitives == 0) return FGS_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (n_primitives == 0) {               // no Gaussian, no term: the camera gradients are zero
+        if (grad_w2c) FGS_HIP(hipMemsetAsync(grad_w2c, 0, 12 * sizeof(float), stream));
+        if (grad_cam_position) FGS_HIP(hipMemsetAsync(grad_cam_position, 0, 3 * sizeof(float), stream));
+        return FGS_OK;
+    }
     if (!means || !scales || !rotations || !opacities || !grad_means || !grad_scales || !grad_rotations || !grad_opacities || !grad_sh_coefficients_0)
         return fail(FGS_ERR_INVALID_ARGUMENT, "NULL parameter / gradient tensor");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (with_pose && !g_fused_single_kernel) return fail(FGS_ERR_INVALID_ARGUMENT, "pose gradients are reduced by the one-kernel K12 only (dev option: the two-kernel form is selected)");
     if (with_maps) { if (int rc = run_blend_backward_aux(P, grad_image, image, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
     else if (int rc = run_blend_backward(P, grad_image, image, stream)) return rc;
 
@@ -454,7 +486,13 @@ int32_t fgs_backward_recycled(const float* grad_image, const float* image, const
         a.live_blocks = live_blocks;
         a.reached_blocks = reached_blocks;
         a.prior_blocks = prior_blocks;
-        FGS_HIP(launch_backward_gradients(a, sh, stream));
+        if (with_pose) {
+            Carver sc(scratch);
+            BackwardScratch::carve(sc, static_cast<uint32_t>(n_primitives), P.geo.n_tiles, true);
+            const PoseScratch ps = PoseScratch::carve(sc, static_cast<uint32_t>(n_primitives));
+            FGS_HIP(launch_backward_gradients_pose(a, sh, PosePart{ps.partials, ps.chunk_sums, grad_w2c, grad_cam_position}, stream));
+        }
+        else FGS_HIP(launch_backward_gradients(a, sh, stream));
     } else {                               // the two-kernel form writes every element and publishes all-ones flags: prior_blocks is not looked at
         if (live_blocks != nullptr) FGS_HIP(hipMemsetAsync(live_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // A/B form: no flags, every block "live"
         if (reached_blocks != nullptr) FGS_HIP(hipMemsetAsync(reached_blocks, 1, (static_cast<size_t>(n_primitives) + 63) / 64, stream));   // ... and "reached"

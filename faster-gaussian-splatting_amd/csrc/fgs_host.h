@@ -144,6 +144,17 @@ struct BackwardScratch {
         return b;
     }
 };
+// fgs_backward_pose only, behind the aux layout of BackwardScratch (fgs_backward_pose_scratch_bytes): one 64-byte line of partial sums per wave of
+// K12 and the fp64 sums of the reduction's first stage (PosePart). Every element that is read is written by the pass itself.
+struct PoseScratch {
+    float* partials; double* chunk_sums;
+    static PoseScratch carve(Carver& c, uint32_t n) {
+        PoseScratch b;
+        b.partials = c.take<float>("pose_partials", ((size_t)n + 63) / 64 * kPoseLineFloats);
+        b.chunk_sums = c.take<double>("pose_chunk_sums", (size_t)kPoseMaxChunks * kPoseLineFloats);
+        return b;
+    }
+};
 // fgs_forward_state::selector, bit 1: the bucket buffer carries ckpt_d (fgs_forward_aux filled it). Bit 0 is the half of the instance double buffer.
 constexpr int32_t kStateDepthCheckpoints = 2;
 

@@ -233,6 +233,22 @@ hipError_t launch_sh_rest_backward(bool fused_adam, const ShRestArgs& a, hipStre
 hipError_t launch_fused_backward_adam(const PreprocessBackwardArgs& a, const ShRestArgs& sh, hipStream_t s);
 // single-view unfused K12 in one kernel: all six gradients written once (sh: grad_sh_rest + SH layout)
 hipError_t launch_backward_gradients(const PreprocessBackwardArgs& a, const ShRestArgs& sh, hipStream_t s);
+// Camera-pose gradients (fgs_backward_pose): the same kernel with POSE set also leaves, per wave of 64 Gaussians, the wave's sums of 15 terms -- 12 for
+// rows 0..2 of w2c (row-major, column 3 = the translation) and 3 for cam_position -- in one 64-byte line of `partials`; two small kernels then add the
+// lines in a fixed order in fp64 (first per chunk of lines into `chunk_sums`, then the chunks) and write grad_w2c [12] / grad_cam_position [3] (either
+// may be nullptr). No float atomics: the result is a deterministic function of K11's records. The additions travel in a struct of their own:
+// PreprocessBackwardArgs stays byte for byte what it is. Only this materialised-gradient kernel has the flag: the fused backward + Adam, sharded,
+// record and asynchronous paths take no pose gradients.
+constexpr int kPoseTerms = 15;          // w2c[0..2][0..3], cam_position[0..2]
+constexpr int kPoseLineFloats = 16;     // one 64-byte line per wave, the last float is padding (written as 0)
+constexpr uint32_t kPoseMaxChunks = 128;
+struct PosePart {
+    float* partials;                      // [ceil(n / 64)][kPoseLineFloats], every line written by the wave that owns the block
+    double* chunk_sums;                   // [kPoseMaxChunks][kPoseLineFloats]
+    float* grad_w2c; float* grad_cam_position;
+};
+struct PreprocessBackwardPoseArgs { PreprocessBackwardArgs k12; PosePart pose; };
+hipError_t launch_backward_gradients_pose(const PreprocessBackwardArgs& a, const ShRestArgs& sh, const PosePart& pose, hipStream_t s);
 
 struct AdamGroup { const float* grad; float* param; float* exp_avg; float* exp_avg_sq; int64_t n; AdamHyper h; uint32_t first_block;
                    uint32_t row_len; };      // floats per Gaussian in this tensor (live_blocks only; 0: read every gradient)

@@ -15,6 +15,9 @@
 //    torch::zeros fills (rasterization_api.cu:127-134, 256 B per Gaussian).
 //  * fused mode never materialises the 59-float gradient: Adam is applied in registers. Invisible Gaussians still
 //    decay their moments and move by momentum (reference: dense zero grads, adam.py:16).
+//  * camera-pose gradients (fgs_backward_pose): backward_gradients_kernel<RT, true> also reduces what the per-Gaussian chains say about w2c and
+//    cam_position -- 15 sums, per wave and then over the waves in a fixed order, no float atomics. Only that materialised-gradient kernel has the flag:
+//    the fused backward + Adam, sharded, record and asynchronous paths take no pose gradients.
 // K13 itself, the optimizer over materialised gradients, is adam.hip; the update and its 16-byte piece are shared through fgs_adam.h.
 #include "fgs_adam.h"
 #include <type_traits>
@@ -43,9 +46,18 @@ template <bool MULTI> __device__ __forceinline__ void sum_into(float& dst, const
 #define FGS_K12_RECORD_EARLY 0   // 1 (A/B): single view, the record is requested together with n_touched -- one dependent step less, 36 B more
                                  // per invisible Gaussian (measured: profiles/k12_unreached_skip.txt)
 #endif
-template <bool FUSED, bool MULTI, bool KEEP_DIR>
+// POSE (backward_gradients_kernel<RT, true>, fgs_backward_pose; single view): the lane's 15 camera terms go to `pose` -- what dcam, dL/d(J W) and dpos
+// say about w2c and cam_position instead of about the mean (layout: PosePart) -- zeros for a Gaussian that is invisible or unreached. Every POSE
+// statement is under `if constexpr`: the other instantiations compile to the instructions they had.
+template <bool FUSED, bool MULTI, bool KEEP_DIR, bool POSE = false>
 __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& a, const unsigned i, const float (&st_p)[14],
-                                                  float (&grad)[14], float (&dir)[3], float (&gcol_out)[3], bool& reached) {
+                                                  float (&grad)[14], float (&dir)[3], float (&gcol_out)[3], bool& reached,
+                                                  [[maybe_unused]] float (&pose)[kPoseTerms]) {
+    static_assert(!POSE || (!MULTI && !FUSED), "pose gradients: the single-view materialised-gradient kernel only");
+    if constexpr (POSE) {
+#pragma unroll
+        for (int k = 0; k < kPoseTerms; ++k) pose[k] = 0.0f;
+    }
     const size_t n = a.n;
     float g_mean[3] = {0.0f, 0.0f, 0.0f}, g_scale[3] = {0.0f, 0.0f, 0.0f}, g_rot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     float g_op[1] = {0.0f}, g_sh0[3] = {0.0f, 0.0f, 0.0f};
@@ -199,6 +211,19 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
 #pragma unroll
         for (int k = 0; k < 3; ++k)                                                    // kb:220-228
             sum_into<MULTI>(g_mean[k], (cam.r1[k] * dcam[0] + cam.r2[k] * dcam[1] + cam.r3[k] * dcam[2]) + dpos[k]);
+        if constexpr (POSE) {
+            // p = W m + t and J W with W = w2c[:3,:3], t = w2c[:3,3]: dL/dt = dL/dp, dL/dW = dL/dp m^T + J^T dL/d(J W); the colour sees mean - cam_position.
+            // dL/dp is dcam plus, on the depth-supervised pass, dL/dz in its third component (z = p.z; launch_depth_mean_gradient is the mean's side of it)
+            const float gp[3] = {dcam[0], dcam[1], V.acc_z != nullptr ? dcam[2] + V.acc_z[i] : dcam[2]};
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                pose[0 + k] = gp[0] * m[k] + P.j11 * djw1[k];
+                pose[4 + k] = gp[1] * m[k] + P.j22 * djw2[k];
+                pose[8 + k] = gp[2] * m[k] + (P.j13 * djw1[k] + P.j23 * djw2[k]);      // j13 = -j11 x_clipped, j23 = -j22 y_clipped
+                pose[4 * k + 3] = gp[k];
+                pose[12 + k] = -dpos[k];
+            }
+        }
         const float* R = P.R; const float* G = P.RSS;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {                                                  // kb:231-240
@@ -225,6 +250,13 @@ __device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& 
 #pragma unroll
     for (int k = 0; k < 4; ++k) grad[10 + k] = g_rot[k];
     return visible;
+}
+// ... without the camera terms: what every kernel but backward_gradients_kernel<RT, true> calls
+template <bool FUSED, bool MULTI, bool KEEP_DIR>
+__device__ __forceinline__ bool gaussian_backward(const PreprocessBackwardArgs& a, const unsigned i, const float (&st_p)[14],
+                                                  float (&grad)[14], float (&dir)[3], float (&gcol_out)[3], bool& reached) {
+    float no_pose[kPoseTerms];            // never touched: every use is under `if constexpr (POSE)`
+    return gaussian_backward<FUSED, MULTI, KEEP_DIR, false>(a, i, st_p, grad, dir, gcol_out, reached, no_pose);
 }
 
 template <bool FUSED, bool MULTI>
@@ -495,9 +527,21 @@ __device__ __forceinline__ bool block_promised_zero(const PreprocessBackwardArgs
     return s0 == 0.0f && s1 == 0.0f && s2 == 0.0f && s3 == 0.0f && s4 == 0.0f && s5 == 0.0f;
 }
 
-template <int RT>
-__global__ void __launch_bounds__(256) backward_gradients_kernel(const PreprocessBackwardArgs a, const ShRestArgs sh) {
+// POSE (backward_gradients_kernel<RT, true>, fgs_backward_pose): the arguments are PreprocessBackwardPoseArgs, the lanes' 15 camera terms are summed over the wave (fgs_wave.h: full
+// EXEC -- only the wave-uniform exits above and below surround it) and lane 63, which holds the sums, stores the wave's line of PosePart::partials.
+// Every wave with first < n stores its line, a wave that reached nothing as zeros, BEFORE the recycled path's early return: the reduction that
+// follows reads every line and nothing of what the scratch held before. Every POSE statement is under `if constexpr`:
+// backward_gradients_kernel<RT, false> compiles to the instructions the kernel had.
+template <bool POSE> using K12ArgsOf = std::conditional_t<POSE, PreprocessBackwardPoseArgs, PreprocessBackwardArgs>;
+__device__ __forceinline__ const PreprocessBackwardArgs& k12_part(const PreprocessBackwardArgs& a) { return a; }
+__device__ __forceinline__ const PreprocessBackwardArgs& k12_part(const PreprocessBackwardPoseArgs& a) { return a.k12; }
+__device__ __forceinline__ float* pose_partials(const PreprocessBackwardArgs&) { return nullptr; }                  // never read: every use is under `if constexpr (POSE)`
+__device__ __forceinline__ float* pose_partials(const PreprocessBackwardPoseArgs& a) { return a.pose.partials; }
+
+template <int RT, bool POSE = false>
+__global__ void __launch_bounds__(256) backward_gradients_kernel(const K12ArgsOf<POSE> args, const ShRestArgs sh) {
     __shared__ __attribute__((aligned(16))) float s_grad[256 / kWave][kWave * 15 * 3];
+    const PreprocessBackwardArgs& a = k12_part(args);
     const WaveBlock w = wave_block<RT>(a.n, sh.total_sh_rest);
     if (w.first >= a.n) return;
     const bool promised_zero = block_promised_zero(a, sh, w);
@@ -506,11 +550,31 @@ __global__ void __launch_bounds__(256) backward_gradients_kernel(const Preproces
     float grad[14], dir[3] = {0.0f, 0.0f, 0.0f}, gcol[3] = {0.0f, 0.0f, 0.0f};
     const float unused[14] = {};
     bool visible = false, reached = false;
-    if (in_range) visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol, reached);
+    [[maybe_unused]] float pose[kPoseTerms];
+    if constexpr (POSE) {
+#pragma unroll
+        for (int k = 0; k < kPoseTerms; ++k) pose[k] = 0.0f;           // the out-of-range lanes of the last wave
+        if (in_range) visible = gaussian_backward<false, false, true, true>(a, i, unused, grad, dir, gcol, reached, pose);
+    } else {
+        if (in_range) visible = gaussian_backward<false, false, true>(a, i, unused, grad, dir, gcol, reached);
+    }
     float* const slice = s_grad[w.wv];
     const bool any_visible = wave_ballot(visible) != 0, any_reached = wave_ballot(reached) != 0;
     if (a.live_blocks != nullptr && w.lane == 0) a.live_blocks[w.first >> 6] = any_visible ? 1 : 0;   // first is a multiple of 64; "visible", not "reached": the flag's contract
     if (a.reached_blocks != nullptr && w.lane == 0) a.reached_blocks[w.first >> 6] = any_reached ? 1 : 0;   // 0: every row of the block is +-0 in all six tensors
+    if constexpr (POSE) {
+        float* const line = pose_partials(args) + (size_t)(w.first >> 6) * kPoseLineFloats;
+        if (any_reached) {                                             // wave-uniform: all 64 lanes take the reductions
+#pragma unroll
+            for (int k = 0; k < kPoseTerms; ++k) {
+                const float total = wave_sum_to_lane63(pose[k]);       // valid in lane 63 only
+                if (w.lane == kWave - 1) line[k] = total;
+            }
+            if (w.lane == kWave - 1) line[kPoseTerms] = 0.0f;
+        } else if (w.lane < static_cast<uint32_t>(kPoseLineFloats)) {
+            line[w.lane] = 0.0f;                                       // 64 lanes of zeros sum to zero: one coalesced store instead
+        }
+    }
     if (!any_reached && promised_zero) return;                         // the zeros are there already: none of the block's 59 x 64 floats is stored
     if (in_range) {
         // scalar stores at a stride of 4 w bytes: the write path combines them. Staging the wave's 64 x w block in LDS and storing it as one
@@ -570,6 +634,57 @@ hipError_t launch_backward_gradients(const PreprocessBackwardArgs& a_in, const S
     a.vector_ok = aligned16(sh.grad_sh_rest) ? 1 : 0;                  // a wave's block starts 64 * R * 12 bytes into the tensor: aligned iff the tensor is
     const dim3 grid((a.n + 255u) / 256u), block(256);
     return dispatch_sh_rest(sh.total_sh_rest, [&](auto rt) { hipLaunchKernelGGL(backward_gradients_kernel<decltype(rt)::value>, grid, block, 0, s, a, sh); });
+}
+
+// ---- the pose partials -> 15 numbers, in a fixed order, accumulated in fp64 ------------------------------------------------------------
+// Thread t of a workgroup of 256 owns term t & 15 and every 16th line from line t >> 4 on: a step of the loop reads 16 consecutive lines (1 KB,
+// coalesced). The 16 sub-sums of a term are then added in ascending order by one thread. Stage 1: one workgroup per chunk of `lines_per_chunk` lines
+// (a multiple of 16) -> chunk_sums[chunk][16] (double). Stage 2: one workgroup adds the chunks the same way and writes the floats. Nothing depends on
+// which workgroup runs when; a line or chunk that does not exist contributes nothing.
+template <class T>
+__device__ __forceinline__ double pose_column_sum(const T* const lines, const uint32_t first, const uint32_t end, double (&s_sub)[16][kPoseLineFloats]) {
+    const uint32_t term = threadIdx.x & 15u, sub = threadIdx.x >> 4;
+    double acc = 0.0;
+    for (uint32_t l = first + sub; l < end; l += 16u) acc += static_cast<double>(lines[(size_t)l * kPoseLineFloats + term]);
+    s_sub[sub][term] = acc;
+    __syncthreads();
+    double total = 0.0;
+    if (sub == 0) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) total += s_sub[k][term];
+    }
+    return total;                                                       // valid in threads 0..15
+}
+
+__global__ void __launch_bounds__(256) pose_chunk_sums_kernel(const PosePart p, const uint32_t n_lines, const uint32_t lines_per_chunk) {
+    __shared__ double s_sub[16][kPoseLineFloats];
+    const uint32_t first = blockIdx.x * lines_per_chunk;
+    const uint32_t end = first + lines_per_chunk < n_lines ? first + lines_per_chunk : n_lines;
+    const double total = pose_column_sum(p.partials, first, end, s_sub);
+    if (threadIdx.x < static_cast<uint32_t>(kPoseLineFloats)) p.chunk_sums[(size_t)blockIdx.x * kPoseLineFloats + threadIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256) pose_final_sum_kernel(const PosePart p, const uint32_t n_chunks) {
+    __shared__ double s_sub[16][kPoseLineFloats];
+    const double total = pose_column_sum(p.chunk_sums, 0u, n_chunks, s_sub);
+    const uint32_t term = threadIdx.x;
+    if (term < 12u) { if (p.grad_w2c != nullptr) p.grad_w2c[term] = static_cast<float>(total); }
+    else if (term < static_cast<uint32_t>(kPoseTerms)) { if (p.grad_cam_position != nullptr) p.grad_cam_position[term - 12u] = static_cast<float>(total); }
+}
+
+hipError_t launch_backward_gradients_pose(const PreprocessBackwardArgs& a_in, const ShRestArgs& sh, const PosePart& pose, hipStream_t s) {
+    if (a_in.n == 0) return hipSuccess;                                // the caller writes the 15 zeros
+    PreprocessBackwardPoseArgs a{a_in, pose};
+    a.k12.vector_ok = aligned16(sh.grad_sh_rest) ? 1 : 0;
+    const dim3 grid((a.k12.n + 255u) / 256u), block(256);
+    const hipError_t e = dispatch_sh_rest(sh.total_sh_rest, [&](auto rt) { hipLaunchKernelGGL((backward_gradients_kernel<decltype(rt)::value, true>), grid, block, 0, s, a, sh); });
+    if (e != hipSuccess) return e;
+    const uint32_t n_lines = (a.k12.n + kWave - 1u) / kWave;
+    const uint32_t per_chunk = ((n_lines + kPoseMaxChunks - 1u) / kPoseMaxChunks + 15u) / 16u * 16u;
+    const uint32_t n_chunks = (n_lines + per_chunk - 1u) / per_chunk;   // <= kPoseMaxChunks
+    hipLaunchKernelGGL(pose_chunk_sums_kernel, dim3(n_chunks), block, 0, s, pose, n_lines, per_chunk);
+    hipLaunchKernelGGL(pose_final_sum_kernel, dim3(1), block, 0, s, pose, n_chunks);
+    return hipGetLastError();
 }
 
 hipError_t launch_fused_backward_adam(const PreprocessBackwardArgs& a_in, const ShRestArgs& sh, hipStream_t s) {

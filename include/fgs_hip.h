@@ -165,6 +165,30 @@ int32_t fgs_backward_recycled(const float* grad_image, const float* image, const
                               float* densification_info, void* scratch,
                               int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                               uint8_t* reached_blocks, const uint8_t* prior_blocks, void* stream);
+/* fgs_backward_recycled that also returns the gradient of the CAMERA: grad_w2c (12 device floats, rows 0..2 of settings->w2c row-major) and
+ * grad_cam_position (3 device floats). With W = w2c[:3,:3], t = w2c[:3,3], c = cam_position and, per Gaussian i that the pass reached, p_i = W m_i + t,
+ * J_i = [[j11, 0, -j11 xc], [0, j22, -j22 yc]] (xc, yc the clipped x/z, y/z), the colour a function of m_i - c:
+ *   grad_w2c[:,3]  = sum_i g_i,                       g_i = dL/dp_i (clip cases as in the mean gradient) + e_2 dL/dz_i (with grad_depth),
+ *   grad_w2c[:,:3] = sum_i (g_i m_i^T + J_i^T dL/d(J_i W)),
+ *   grad_cam_position = - sum_i dL/d(m_i - c)         (exactly 0 when active_sh_bases == 1).
+ * w2c and cam_position are INDEPENDENT inputs, as in fgs_settings: the relation c = -W^T t is the caller's chain rule. The proper-antialiasing opacity
+ * factor is a constant here as everywhere. The sums are formed inside K12 -- per wave of 64 Gaussians, then over the waves in a fixed order in fp64, no
+ * float atomics: a deterministic function of the per-Gaussian sums of the backward blend pass -- and do not depend on what `scratch` held.
+ * Either output may be NULL; both NULL is fgs_backward_recycled exactly and takes its scratch size, otherwise scratch:
+ * fgs_backward_pose_scratch_bytes(), with or without map gradients. grad_alpha / grad_depth are accepted as by fgs_backward_aux. n_primitives == 0
+ * writes 15 zeros. The six parameter gradients, both flag arrays and densification_info are what fgs_backward_recycled leaves. Only this
+ * materialised-gradient pass has camera gradients: the fused backward + Adam, sharded, record and asynchronous paths take none, and there is none
+ * for the intrinsics. */
+size_t fgs_backward_pose_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height);
+int32_t fgs_backward_pose(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                          const float* means, const float* scales, const float* rotations, const float* opacities,
+                          const float* sh_coefficients_rest,
+                          void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                          float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                          float* densification_info, void* scratch,
+                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                          uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream);
 
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
