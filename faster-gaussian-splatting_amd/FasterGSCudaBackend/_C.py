@@ -20,6 +20,8 @@ The four scratch tensors are opaque uint8 blobs exactly as in the reference (uti
 callback, handed back to `backward` untouched); the three integers are the reference's (n_instances, n_buckets, selector). The
 number of visible primitives -- a fourth piece of state this backend's sharded multi-GPU path uses -- stays in the primitive blob
 on the device, so nothing is smuggled through the integers.
+`selector` is opaque, as in the reference: bit 0 is the half of the instance double buffer, the higher bits are flags of the library
+(include/fgs_hip.h: fgs_forward_state) -- hand it back to `backward` as it came, do not read it as 0 / 1.
 """
 from __future__ import annotations
 

@@ -357,12 +357,76 @@ class Backend:
         self._check(self.lib.fgs_backward_pose(*args, _ptr(grad_w2c), _ptr(grad_cam), _stream_of(device)), 'fgs_backward_pose')
         return grads + (grad_w2c, grad_cam)
 
+    @staticmethod
+    def _check_features(features: torch.Tensor, n: int, device: torch.device) -> int:
+        """The channel count F of a [N, F] feature tensor, 1..64 (an empty tensor has no address the library could be handed to refuse it itself)."""
+        if features.dim() != 2 or features.shape[0] != n or features.dtype != torch.float32 or not features.is_contiguous() or features.device != device:
+            raise RuntimeError(f'features must be a contiguous float32 [N, F] = [{n}, F] tensor on the parameters\' device, not '
+                               f'{tuple(features.shape)} {features.dtype} on {features.device}')
+        if not 1 <= features.shape[1] <= 64:
+            raise RuntimeError(f'features has {features.shape[1]} channels: the feature render takes 1..64 channels')
+        return int(features.shape[1])
+
+    def blend_features(self, features: torch.Tensor, result, n_primitives: int, settings: RasterizerSettings) -> torch.Tensor:
+        """fgs_blend_features: feature_map [F,H,W] = sum_i w_i features[i] over the pairs the training blend of `result` (a synchronous forward /
+        forward_aux over `n_primitives` Gaussians with these settings) blended. features: float32 [N, F], any sign, 1 <= F <= 64."""
+        device = result.image.device
+        n = int(n_primitives)
+        f = self._check_features(features, n, device)
+        keep: list = []
+        S = self._settings(settings, int(settings.active_sh_bases) - 1, device, keep)      # the blend reads no SH coefficient: any consistent count
+        st = _lib.ForwardState(*result.state)
+        fmap = torch.empty((f, int(settings.height), int(settings.width)), dtype=torch.float32, device=device)
+        b = result.buffers
+        self._check(self.lib.fgs_blend_features(_ptr(features), f, _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), n, C.byref(S), C.byref(st),
+                                                fmap.data_ptr(), _stream_of(device)), 'fgs_blend_features')
+        return fmap
+
+    def backward_features(self, densification_info, grad_image, grad_feature_map, image, feature_map, features, means, scales, rotations, opacities,
+                          sh_rest, buffers, settings, state, detach_geometry: bool = False, live_blocks: Optional[torch.Tensor] = None,
+                          reached_blocks: Optional[torch.Tensor] = None) -> tuple:
+        """fgs_backward_features: the six gradients of `backward` plus grad_features [N, F], for a loss that also depends on the map of
+        `blend_features`. grad_feature_map [F,H,W] or None: None is `backward` exactly and the seventh result is None. detach_geometry: the feature
+        term reaches grad_features only. Gradients come back in fresh tensors."""
+        if grad_feature_map is None:
+            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state,
+                                 live_blocks=live_blocks, reached_blocks=reached_blocks) + (None,)
+        device = self._check_params((means, scales, rotations, opacities, sh_rest), BACKWARD_PARAMETER_NAMES)
+        n = means.shape[0]
+        f = self._check_features(features, n, device)
+        shape = (f, int(settings.height), int(settings.width))
+        for name, t in (('feature_map', feature_map), ('grad_feature_map', grad_feature_map)):
+            if tuple(t.shape) != shape or t.device != device:
+                raise RuntimeError(f'{name} must be a [F,H,W] = {shape} tensor on the parameters\' device')
+        feature_map = feature_map.to(dtype=torch.float32).contiguous()
+        grad_feature_map = grad_feature_map.to(dtype=torch.float32).contiguous()
+        grad_image = grad_image.to(dtype=torch.float32).contiguous()
+        keep: list = []
+        total_rest = total_sh_rest(sh_rest)
+        S = self._settings(settings, total_rest, device, keep)
+        grads = _gradients_out(None, gradient_shapes(n, total_rest), device)
+        grad_features = torch.empty((n, f), dtype=torch.float32, device=device)
+        dens = _densification(densification_info, n, device, validate=True)
+        _check_block_flags('live_blocks', live_blocks, n, device)
+        _check_block_flags('reached_blocks', reached_blocks, n, device)
+        scratch = self._scratch(n, settings, device)
+        st = _lib.ForwardState(*state)
+        self._check(self.lib.fgs_backward_features(
+            _ptr(grad_image), _ptr(image), None, None, None, _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh_rest),
+            _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
+            _ptr(grads[4]), _ptr(grads[5]), _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+            _ptr(features), f, _ptr(feature_map), grad_feature_map.data_ptr(), _ptr(grad_features),
+            int(bool(detach_geometry)), _stream_of(device)), 'fgs_backward_features')
+        return grads + (grad_features,)
+
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
                             buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,
-                            grad_alpha=None, grad_depth=None) -> None:
+                            grad_alpha=None, grad_depth=None, grad_feature_map=None) -> None:
         """params / moments / lrs in optimizer-group order: means, sh0, sh_rest, opacities, scales, rotations (Model.py:238-245)."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_adam_fused takes no alpha / depth gradients: use backward_aux and an optimizer step of its own')
+        if grad_feature_map is not None:
+            raise RuntimeError('backward_adam_fused takes no feature-map gradient: use backward_features and an optimizer step of its own')
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         keep: list = []
         n = params[0].shape[0]
@@ -509,10 +573,13 @@ class Backend:
         return ForwardResult(image, tuple(buffers), _state_tuple(st))
 
     def backward_to_records(self, grad_image, image, buffers, settings: RasterizerSettings, state, total_sh_rest: int,
-                            out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None) -> torch.Tensor:
+                            out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None,
+                            grad_feature_map=None) -> torch.Tensor:
         """K11 of a view rendered by `forward_from_records` -> float32 [n_records, 9] accumulator records."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_to_records takes no alpha / depth gradients: the sharded and record paths render colour only')
+        if grad_feature_map is not None:
+            raise RuntimeError('backward_to_records takes no feature-map gradient: the sharded and record paths render colour only')
         device = image.device
         n = int(state[0])
         keep: list = []

@@ -540,6 +540,55 @@ def diff_rasterize_pose(means: torch.Tensor, scales: torch.Tensor, rotations: to
     return image, (a if alpha else None), (d if depth else None)
 
 
+class _RasterizeFeatures(torch.autograd.Function):
+    """_Rasterize that also blends F per-Gaussian feature channels with the compositing weights of the same pass, differentiable in the features and --
+    unless detach_geometry -- through the weights in the Gaussians (fgs_blend_features / fgs_backward_features). Always the synchronous forward pass;
+    gradients in fresh tensors (no arena, no live-block hand-over)."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, features,
+                rasterizer_settings: RasterizerSettings, detach_geometry: bool):
+        _require_gpu(means)
+        be = default_backend()
+        res = be.forward(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, rasterizer_settings)
+        feature_map = be.blend_features(features, res, means.shape[0], rasterizer_settings)
+        ctx.rasterizer_settings = rasterizer_settings
+        ctx.buffer_state = res.state
+        ctx.detach_geometry = bool(detach_geometry)
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None (= zero), not as a tensor of zeros
+        ctx.save_for_backward(res.image, feature_map, features, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.mark_non_differentiable(densification_info)
+        return res.image, feature_map
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_feature_map):
+        image, feature_map, features, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        clear_live_blocks([means])
+        # a feature map that is not part of the loss costs nothing: the pass is then the plain one and the features get no gradient
+        *grads, grad_features = default_backend().backward_features(
+            ctx.densification_info, grad_image.contiguous(), grad_feature_map.contiguous() if grad_feature_map is not None else None, image, feature_map,
+            features, means, scales, rotations, opacities, sh_rest, buffers, ctx.rasterizer_settings, ctx.buffer_state, ctx.detach_geometry)
+        return (*grads, None, grad_features if ctx.needs_input_grad[7] else None, None, None)
+
+
+def diff_rasterize_features(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                            sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                            rasterizer_settings: RasterizerSettings, features: torch.Tensor, detach_geometry: bool = False):
+    """Training render that also returns, differentiable, the blend of per-Gaussian feature channels: (image [3,H,W], feature_map [F,H,W]) with
+    feature_map[c] = sum_i w_i features[i, c] over the pairs the image blended (w_i = T_i alpha_i; no background term, not normalised: divide by the
+    accumulated opacity -- a channel of ones -- for a mean). `features`: float32 [N, F], any sign, 1 <= F <= 64: semantic or language features, normals,
+    ids, an appearance code. One forward and one backward pass whatever F. detach_geometry=True: the feature loss trains the features only (the
+    Gaussians get the image's gradients). The image is diff_rasterize's."""
+    if features.dtype != torch.float32 or not features.is_contiguous():          # shape and channel count are the backend's to refuse
+        features = features.to(torch.float32).contiguous()
+    return _RasterizeFeatures.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, features,
+                                    rasterizer_settings, bool(detach_geometry))
+
+
 def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
               sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
               to_chw: bool, clamp_output: bool = True) -> torch.Tensor:

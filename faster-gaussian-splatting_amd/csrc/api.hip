@@ -208,7 +208,8 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
         StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_blend_aux(ba, stream));
     }
     else { StageScope t(ST_BLEND_FORWARD, stream); FGS_HIP(launch_blend(training, ba, stream)); }   // K10 (fwd:239)
-    *rq.state_out = fgs_forward_state{static_cast<int32_t>(n_visible), static_cast<int32_t>(n_instances), static_cast<int32_t>(n_buckets_cap), tile_sel};
+    const int32_t origin = (counts.on_device ? kStateAsyncCounts : 0) | (training && rq.n > 0 && !rq.params.means ? kStateFromRecords : 0);
+    *rq.state_out = fgs_forward_state{static_cast<int32_t>(n_visible), static_cast<int32_t>(n_instances), static_cast<int32_t>(n_buckets_cap), tile_sel | origin};
     return FGS_OK;
 }
 
@@ -273,6 +274,48 @@ int run_blend_backward_aux(const BackwardPlan& P, const float* grad_image, const
     a.d.clear_z_f4 = static_cast<uint32_t>(static_cast<size_t>(reinterpret_cast<char*>(P.sc.acc_z_hot + BackwardScratch::kHotDepthFloats) - reinterpret_cast<char*>(P.sc.acc_z)) / 16);
     { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels_depth(a, stream)); }
     { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward_depth(a, stream)); }
+    return FGS_OK;
+}
+
+// ---- the feature-channel render (blend_features.hip) ----
+// What fgs_backward_features adds to a backward pass. n: the Gaussian count, for the clear of grad_features.
+struct FeatureGradient { const float* features; int32_t n_channels; const float* feature_map; const float* grad_feature_map; float* grad_features;
+                         int32_t detach_geometry; int32_t n; };
+
+static int check_feature_channels(int32_t n_channels, const fgs_forward_state* state) {
+    if (n_channels < 1 || n_channels > kMaxFeatureChannels)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "n_channels %d: the feature render takes 1..%d channels", n_channels, kMaxFeatureChannels);
+    if (state->selector & kStateAsyncCounts)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "the feature render needs the buffers of a synchronous forward pass (fgs_forward / fgs_forward_aux), these are fgs_forward_async's");
+    if (state->selector & kStateFromRecords)
+        return fail(FGS_ERR_INVALID_ARGUMENT, "the feature render does not take the sharded / record paths: these buffers were filled from splat records");
+    return FGS_OK;
+}
+
+static int check_feature_gradient(const FeatureGradient& f, const fgs_forward_state* state) {
+    if (int rc = check_feature_channels(f.n_channels, state)) return rc;
+    if (f.n > 0 && (!f.features || !f.feature_map || !f.grad_features)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL features / feature_map / grad_features");
+    return FGS_OK;
+}
+
+static FeatureBlendArgs feature_blend_args(const PrimitiveBuffers& pb, const TileBuffers& tb, const InstanceBuffers& ib, const Geometry& geo,
+                                           const fgs_settings& settings, const fgs_forward_state& state, const float* features, int32_t n_channels) {
+    FeatureBlendArgs a{};
+    a.ranges = tb.ranges; a.inst_prims = ib.prims[state.selector & 1]; a.rec = pb.rec;
+    a.n_processed = tb.n_processed; a.max_n_processed = tb.max_n_processed;
+    a.features = features; a.n_channels = static_cast<uint32_t>(n_channels);
+    a.width = settings.width; a.height = settings.height; a.grid_w = geo.grid_w; a.grid_h = geo.grid_h; a.n_tiles = geo.n_tiles;
+    a.proper_aa = settings.proper_antialiasing ? 1 : 0;
+    return a;
+}
+
+static int run_blend_features_backward(const BackwardPlan& P, const FeatureGradient& f, hipStream_t stream) {
+    FeatureBlendArgs a = feature_blend_args(P.pb, P.tb, P.ib, P.geo, *P.settings, *P.state, f.features, f.n_channels);
+    a.feature_map_in = f.feature_map; a.grad_feature_map = f.grad_feature_map; a.grad_features = f.grad_features; a.acc = P.pb.acc;
+    a.detach_geometry = f.detach_geometry ? 1 : 0;
+    FGS_HIP(hipMemsetAsync(f.grad_features, 0, sizeof(float) * static_cast<size_t>(f.n) * f.n_channels, stream));
+    StageScope t(ST_BLEND_BACKWARD, stream);
+    FGS_HIP(launch_blend_features_backward(a, stream));
     return FGS_OK;
 }
 }  // namespace fgs
@@ -436,18 +479,18 @@ size_t fgs_backward_pose_scratch_bytes(int32_t n_primitives, int32_t width, int3
     return c.total();
 }
 
-// fgs_backward_recycled that also reduces, inside K12, what the per-Gaussian chains say about the camera: dL/dw2c (rows 0..2) and dL/dcam_position.
-// Both outputs NULL: the pass is fgs_backward_recycled's, kernel for kernel, on the plain (or aux) scratch layout. Otherwise the scratch has the aux
-// layout -- whether or not map gradients arrive: the plain layout is its prefix -- with the pose partials behind it.
-int32_t fgs_backward_pose(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
-                          const float* means, const float* scales, const float* rotations, const float* opacities,
-                          const float* sh_coefficients_rest,
-                          void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
-                          float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
-                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
-                          float* densification_info, void* scratch,
-                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
-                          uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream_) {
+// The materialised-gradient backward pass of the single-GPU path: staging + K11, the feature backward blend if `feat` brings an upstream gradient of a
+// feature map, K12. Behind fgs_backward_pose (feat == nullptr) and fgs_backward_features.
+static int backward_pass(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                         const float* means, const float* scales, const float* rotations, const float* opacities,
+                         const float* sh_coefficients_rest,
+                         void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                         float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                         float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                         float* densification_info, void* scratch,
+                         int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                         uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, const FeatureGradient* feat,
+                         void* stream_) {
     const bool with_pose = grad_w2c != nullptr || grad_cam_position != nullptr;
     if (prior_blocks != nullptr && reached_blocks == nullptr)
         return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks without reached_blocks: the caller could not make the promise again for the next pass");
@@ -460,6 +503,7 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
     if (grad_depth && !(state->selector & kStateDepthCheckpoints))
         return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth needs the depth checkpoints that fgs_forward_aux writes: these buffers were filled by a forward pass without them");
     if (grad_depth && !depth_expected) return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth without depth_expected (the map fgs_forward_aux returned)");
+    if (feat) { if (int rc = check_feature_gradient(*feat, state)) return rc; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (n_primitives == 0) {               // no Gaussian, no term: the camera gradients are zero
         if (grad_w2c) FGS_HIP(hipMemsetAsync(grad_w2c, 0, 12 * sizeof(float), stream));
@@ -471,6 +515,8 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
     if (with_pose && !g_fused_single_kernel) return fail(FGS_ERR_INVALID_ARGUMENT, "pose gradients are reduced by the one-kernel K12 only (dev option: the two-kernel form is selected)");
     if (with_maps) { if (int rc = run_blend_backward_aux(P, grad_image, image, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
     else if (int rc = run_blend_backward(P, grad_image, image, stream)) return rc;
+    // behind K11's last kernel (the hot replicas are folded, the records are marked dirty), in front of K12: the feature term adds into the same records
+    if (feat) { if (int rc = run_blend_features_backward(P, *feat, stream)) return rc; }
 
     PreprocessBackwardArgs a{};
     ShRestArgs sh{};
@@ -501,6 +547,70 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
     }
     // z_i's own dependence on mean_i: grad_means += dL/dz w2c[2, 0:3], after K12 has written every element. Not launched without a depth gradient.
     if (grad_depth) { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_depth_mean_gradient(P.sc.acc_z, P.pb.n_touched, settings->w2c, grad_means, static_cast<uint32_t>(n_primitives), stream)); }
+    return FGS_OK;
+}
+
+// fgs_backward_recycled that also reduces, inside K12, what the per-Gaussian chains say about the camera: dL/dw2c (rows 0..2) and dL/dcam_position.
+// Both outputs NULL: the pass is fgs_backward_recycled's, kernel for kernel, on the plain (or aux) scratch layout. Otherwise the scratch has the aux
+// layout -- whether or not map gradients arrive: the plain layout is its prefix -- with the pose partials behind it.
+int32_t fgs_backward_pose(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                          const float* means, const float* scales, const float* rotations, const float* opacities,
+                          const float* sh_coefficients_rest,
+                          void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                          float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                          float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                          float* densification_info, void* scratch,
+                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                          uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream_) {
+    return backward_pass(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                         primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                         grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                         reached_blocks, prior_blocks, grad_w2c, grad_cam_position, nullptr, stream_);
+}
+
+// fgs_backward_reached with the upstream gradient of a feature map of fgs_blend_features: K11 as always, then the feature backward blend -- grad_features
+// by atomics into memory zeroed here, its geometry term into words 0..5 of K11's accumulator records unless detach_geometry -- then K12, which turns the
+// records into the six gradients unchanged. grad_feature_map == NULL is fgs_backward_reached exactly: the feature arguments are not looked at.
+int32_t fgs_backward_features(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                              const float* means, const float* scales, const float* rotations, const float* opacities,
+                              const float* sh_coefficients_rest,
+                              void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                              float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                              float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                              float* densification_info, void* scratch,
+                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                              uint8_t* reached_blocks, const float* features, int32_t n_channels, const float* feature_map,
+                              const float* grad_feature_map, float* grad_features, int32_t detach_geometry, void* stream_) {
+    const FeatureGradient feat{features, n_channels, feature_map, grad_feature_map, grad_features, detach_geometry, n_primitives};
+    return backward_pass(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                         primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                         grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                         reached_blocks, nullptr, nullptr, nullptr, grad_feature_map ? &feat : nullptr, stream_);
+}
+
+// The F-channel blend over the buffers of a completed synchronous training forward pass (fgs_forward / fgs_forward_aux): feature_map [F,H,W].
+int32_t fgs_blend_features(const float* features, int32_t n_channels, const void* primitive_buffers, const void* tile_buffers, const void* instance_buffers,
+                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, float* feature_map, void* stream_) {
+    if (int rc = check_settings(settings)) return rc;
+    if (!state || n_primitives < 0) return fail(FGS_ERR_INVALID_ARGUMENT, "bad state / n_primitives");
+    if (int rc = check_feature_channels(n_channels, state)) return rc;
+    if (!feature_map) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL feature_map");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const Geometry geo = geometry_of(settings->width, settings->height);
+    if (n_primitives == 0) {               // nothing was blended: a zero map, nothing else is touched
+        FGS_HIP(hipMemsetAsync(feature_map, 0, sizeof(float) * n_channels * static_cast<size_t>(settings->width) * settings->height, stream));
+        return FGS_OK;
+    }
+    if (!features) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL features");
+    if (!primitive_buffers || !tile_buffers || (state->n_instances > 0 && !instance_buffers)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL scratch buffer");
+    Carver pc(const_cast<void*>(primitive_buffers)), tc(const_cast<void*>(tile_buffers)), ic(const_cast<void*>(instance_buffers));
+    const PrimitiveBuffers pb = PrimitiveBuffers::carve(pc, static_cast<uint32_t>(n_primitives));
+    const TileBuffers tb = TileBuffers::carve(tc, geo.n_tiles, true);
+    const InstanceBuffers ib = InstanceBuffers::carve(ic, static_cast<uint32_t>(state->n_instances), geo.key_bytes, geo.end_bit);
+    FeatureBlendArgs a = feature_blend_args(pb, tb, ib, geo, *settings, *state, features, n_channels);
+    a.feature_map = feature_map;
+    StageScope t(ST_BLEND_FORWARD, stream);
+    FGS_HIP(launch_blend_features(a, stream));
     return FGS_OK;
 }
 

@@ -157,6 +157,9 @@ struct PoseScratch {
 };
 // fgs_forward_state::selector, bit 1: the bucket buffer carries ckpt_d (fgs_forward_aux filled it). Bit 0 is the half of the instance double buffer.
 constexpr int32_t kStateDepthCheckpoints = 2;
+// bit 2: the counts of the state are bounds (fgs_forward_async); bit 3: the primitive blob was filled from splat records, not by K1 over the caller's
+// Gaussians (fgs_forward_from_records / _shard_records). Read by the feature render, which takes neither.
+constexpr int32_t kStateAsyncCounts = 4, kStateFromRecords = 8;
 
 // One blob from the caller's allocator: size it for B::carve(args...), ask `resize` for buffer `which`, carve it into `out`.
 template <class B, class... A>

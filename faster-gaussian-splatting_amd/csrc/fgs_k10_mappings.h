@@ -1,4 +1,4 @@
-// K10's tile -> workgroup mappings (included by blend_forward.hip alone): the six that were built and measured, selected at run time by
+// K10's tile -> workgroup mappings (included by blend_forward.hip, and by blend_features.hip for the columns mapping): the six that were built and measured, selected at run time by
 // BlendArgs::row_group, and the history of their measurements. The product library always passes kColumnsTopDown (api.hip); the dev library passes what
 // fgs_debug_set_option(10, ..) set. The product kernels still compile all six arms: with the columns arm alone they are 240 instructions shorter each,
 // but the allocator then puts two more moves and a wait into the walk's trip of blend_kernel<true>, and K10 measured 1 - 2 % slower in 14 of 14
@@ -83,8 +83,9 @@ __device__ __forceinline__ unsigned tile_of_workgroup(const unsigned block, cons
 // motivated it gains nothing from balance alone -- the device-side block plan, which balances it, measures 0.366 against 0.387 ms -- because its span is
 // the serial walk of single tiles with lists of thousands (389 us for one tile of 3 860 walked entries). Removed.
 // the launch grid of a mapping: its tiles and its padding workgroups. A mapping that reads the plan is launched with one (api.hip: bucket_scan_and_mapping).
+static unsigned columns_grid(const unsigned grid_w, const unsigned grid_h) { return kXcds * ((grid_w + kXcds - 1) / kXcds) * grid_h; }   // kColumnsTopDown / kColumnsBottomUp
 static unsigned blend_grid(const BlendArgs& a) {
-    if (a.row_group == kColumnsTopDown || a.row_group == kColumnsBottomUp) return kXcds * ((a.grid_w + kXcds - 1) / kXcds) * a.grid_h;
+    if (a.row_group == kColumnsTopDown || a.row_group == kColumnsBottomUp) return columns_grid(a.grid_w, a.grid_h);
     if (a.row_group == kBandsThroughPlan) return ((a.n_tiles + kXcds - 1) / kXcds) * kXcds;
     if (a.row_group == kPlannedBlocks)
         return kPlanBlocks * ((a.grid_w + kPlanBlocksX - 1) / kPlanBlocksX) * ((a.grid_h + kPlanBlocksY - 1) / kPlanBlocksY);

@@ -187,6 +187,25 @@ hipError_t launch_blend_backward_depth(const BlendBackwardDepthArgs& a, hipStrea
 // after K12: grad_means[i] += acc_z[i] * w2c[2, 0:3] for the Gaussians with n_touched != 0 -- all that z_i's own dependence on mean_i contributes
 hipError_t launch_depth_mean_gradient(const float* acc_z, const uint32_t* n_touched, const float* w2c, float* grad_means, uint32_t n, hipStream_t s);
 
+// blend_features.hip: F per-Gaussian feature channels blended with the compositing weights of a completed training forward pass (fgs_blend_features),
+// and the backward pass of that blend (fgs_backward_features), which runs between K11 and K12. Both walk the tile lists K10 built, bounded per
+// pixel by n_processed.
+constexpr int kMaxFeatureChannels = 64;
+struct FeatureBlendArgs {
+    const uint2* ranges; const uint32_t* inst_prims; const PrimRec* rec;
+    const uint32_t* n_processed; const uint32_t* max_n_processed;          // tile-major [T][192], [T]: what K10 left
+    const float* features;                // [N][F]
+    float* feature_map;                   // forward: [F][H][W], every element written
+    const float* feature_map_in;          // backward: the forward pass's map
+    const float* grad_feature_map;        // backward: [F][H][W]
+    float* grad_features;                 // backward: [N][F], zero at launch, added to with float atomics
+    float* acc;                           // backward: K11's accumulator records [N][9]; words 0..5 are added to unless detach_geometry
+    uint32_t n_channels, width, height, grid_w, grid_h, n_tiles;
+    int proper_aa, detach_geometry;
+};
+hipError_t launch_blend_features(const FeatureBlendArgs& a, hipStream_t s);
+hipError_t launch_blend_features_backward(const FeatureBlendArgs& a, hipStream_t s);
+
 struct AdamHyper { float step_size, beta1, beta2, eps, bc2_sqrt_rcp; };
 
 struct BackwardView {                   // what K12 needs per camera view (one on the single-GPU path, up to kMaxBatchViews on the sharded path)

@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_aux, rasterize, rasterize_aux
+from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_aux, diff_rasterize_features, rasterize, rasterize_aux
 
 from .scenes import View
 
@@ -78,6 +78,15 @@ def render_image_training_aux(g: Gaussians, view: View, update_densification_inf
     return diff_rasterize_aux(*g.tensors(),
                               densification_info=g.densification_info if update_densification_info else torch.empty(0),
                               rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), alpha=alpha, depth=depth)
+
+
+def render_image_training_features(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, features: torch.Tensor,
+                                   detach_geometry: bool = False):
+    """render_image_training plus the differentiable blend of per-Gaussian feature channels [N, F]: (image, feature_map [F,H,W])."""
+    return diff_rasterize_features(*g.tensors(),
+                                   densification_info=g.densification_info if update_densification_info else torch.empty(0),
+                                   rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), features=features,
+                                   detach_geometry=detach_geometry)
 
 
 def depth_l1_loss(alpha: torch.Tensor, depth: torch.Tensor, depth_target: torch.Tensor, valid: 'torch.Tensor | None' = None) -> torch.Tensor:

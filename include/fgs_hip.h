@@ -61,7 +61,8 @@ typedef struct fgs_forward_state {
     int32_t n_visible;
     int32_t n_instances;
     int32_t n_buckets;   /* capacity of the bucket buffer (upper bound of the device-side count) */
-    int32_t selector;    /* bit 0: which half of the instance double buffer holds the tile-sorted list; bit 1: fgs_forward_aux left depth checkpoints */
+    int32_t selector;    /* bit 0: which half of the instance double buffer holds the tile-sorted list; bit 1: fgs_forward_aux left depth checkpoints;
+                            bit 2: the counts are bounds (fgs_forward_async); bit 3: the buffers were filled from splat records */
 } fgs_forward_state;
 
 int32_t fgs_abi_version(void);
@@ -189,6 +190,37 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
                           float* densification_info, void* scratch,
                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                           uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream);
+
+/* Feature-channel render of the training pass. features: fp32 [n_primitives, n_channels] contiguous, any sign, 1 <= n_channels <= 64. Over exactly the
+ * (pixel, Gaussian) pairs the training blend of the forward pass blended, in its order -- the same sub-tile cull, alpha >= 1/255, T_before >= 1e-4, never
+ * beyond the pixel's last contributor -- with w_i = T_before_i alpha_i:
+ *     feature_map[c][p] = sum_i w_i features[i][c]            fp32 [n_channels, H, W], every element written
+ * No background term, no normalisation; 0 where nothing was blended. A channel of ones is 1 - T_final, a channel holding the view-space depth z_i is
+ * fgs_forward_aux's depth_expected. The buffers and `state` are those of a completed SYNCHRONOUS fgs_forward or fgs_forward_aux over the same Gaussians
+ * and settings; they are read only, and stay valid input to every backward pass. One walk per 16 channels (4 or 8 for a narrower F).
+ * FGS_ERR_INVALID_ARGUMENT, never ignored: n_channels outside 1..64, NULL features (n_primitives > 0) or feature_map, buffers of fgs_forward_async or of
+ * the record / sharded forward passes. n_primitives == 0: a zero map, nothing else is written. */
+int32_t fgs_blend_features(const float* features, int32_t n_channels, const void* primitive_buffers, const void* tile_buffers, const void* instance_buffers,
+                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, float* feature_map, void* stream);
+/* fgs_backward_reached for a loss that also depends on such a map: feature_map = what fgs_blend_features returned, grad_feature_map = its upstream
+ * gradient [n_channels, H, W]. With u_i(p) = sum_c features[i][c] grad_feature_map[c][p] and S_i(p) = sum_{j>i} w_j u_j = sum_c feature_map[c][p]
+ * grad_feature_map[c][p] - sum_{j<=i} w_j u_j (the forward map takes the place of per-bucket checkpoints):
+ *     grad_features[i][c] = sum_p w_i grad_feature_map[c][p]                       fp32 [n_primitives, n_channels], need not be initialised
+ *     dL/dalpha_i(p)     += T_i u_i - S_i / max(1 - alpha_i, 1e-6)                  added to the colour term's per-Gaussian sums, then K12 as always
+ * The kernels run K11, the feature backward blend, K12. detach_geometry != 0: grad_features only, the six parameter gradients are fgs_backward_reached's.
+ * grad_feature_map == NULL IS fgs_backward_reached: the feature arguments are not looked at. scratch: as for the pass without features
+ * (fgs_backward_scratch_bytes, or fgs_backward_aux_scratch_bytes with map gradients). Refused like fgs_blend_features; the fused backward + Adam,
+ * asynchronous, sharded and record paths and the pose gradients take no feature gradient. n_primitives == 0 writes nothing. */
+int32_t fgs_backward_features(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                              const float* means, const float* scales, const float* rotations, const float* opacities,
+                              const float* sh_coefficients_rest,
+                              void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                              float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                              float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                              float* densification_info, void* scratch,
+                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                              uint8_t* reached_blocks, const float* features, int32_t n_channels, const float* feature_map,
+                              const float* grad_feature_map, float* grad_features, int32_t detach_geometry, void* stream);
 
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
