@@ -283,6 +283,9 @@ class Backend:
     def _scratch_pose(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
         return _empty_bytes(self.lib.fgs_backward_pose_scratch_bytes(n, int(settings.width), int(settings.height)), device)
 
+    def _scratch_absgrad(self, n: int, settings: RasterizerSettings, device: torch.device) -> torch.Tensor:
+        return _empty_bytes(self.lib.fgs_backward_absgrad_scratch_bytes(n, int(settings.width), int(settings.height)), device)
+
     def backward(self, densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings,
                  state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
                  reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None) -> tuple:
@@ -315,10 +318,21 @@ class Backend:
         return self._backward(densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest, buffers,
                               settings, state, out, live_blocks, reached_blocks, prior_blocks, (w2c, cam_position))
 
+    def backward_absgrad(self, densification_info, abs_densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations,
+                         opacities, sh_rest, buffers, settings, state, out: tuple | None = None, live_blocks: Optional[torch.Tensor] = None,
+                         reached_blocks: Optional[torch.Tensor] = None, prior_blocks: Optional[torch.Tensor] = None) -> tuple:
+        """`backward_aux` that also accumulates the absolute-gradient densification statistic (fgs_backward_absgrad) into `abs_densification_info`,
+        float32 [2, N] like `densification_info`: row 0 += 1 per visible Gaussian, row 1 += sqrt((0.5 W sum_p |gx_p|)^2 + (0.5 H sum_p |gy_p|)^2), the
+        per-pixel shares of dL/dmean2d summed by magnitude instead of by sign. None or an empty tensor is `backward_aux` exactly. `densification_info` may be
+        given as well or be None; the two may not be the same memory. Map gradients may be None."""
+        return self._backward(densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest, buffers,
+                              settings, state, out, live_blocks, reached_blocks, prior_blocks, abs_info=abs_densification_info)[:6]
+
     def _backward(self, densification_info, grad_image, grad_alpha, grad_depth, image, depth, means, scales, rotations, opacities, sh_rest,
-                  buffers, settings, state, out, live_blocks, reached_blocks, prior_blocks, camera: 'tuple | None' = None) -> tuple:
-        """The materialised-gradient backward pass behind backward / backward_aux (camera=None: fgs_backward_recycled) and backward_pose
-        (camera = which of (grad_w2c, grad_cam_position) are wanted: fgs_backward_pose): the six gradients + (grad_w2c, grad_cam_position)."""
+                  buffers, settings, state, out, live_blocks, reached_blocks, prior_blocks, camera: 'tuple | None' = None, abs_info=None) -> tuple:
+        """The materialised-gradient backward pass behind backward / backward_aux (camera=None: fgs_backward_recycled), backward_pose
+        (camera = which of (grad_w2c, grad_cam_position) are wanted: fgs_backward_pose) and backward_absgrad (abs_info: fgs_backward_absgrad): the six
+        gradients + (grad_w2c, grad_cam_position)."""
         aux = grad_alpha is not None or grad_depth is not None
         want_w2c, want_cam = camera if camera is not None else (False, False)
         pose = want_w2c or want_cam
@@ -340,15 +354,22 @@ class Backend:
         depth = depth.to(dtype=torch.float32).contiguous() if grad_depth is not None else None
         grads = _gradients_out(out, gradient_shapes(n, total_rest), device)
         dens = _densification(densification_info, n, device, validate=True)
+        try:
+            absd = _densification(abs_info, n, device, validate=True)
+        except RuntimeError as e:
+            raise RuntimeError('abs_' + str(e)) from None
         _check_block_flags('live_blocks', live_blocks, n, device)
         _check_block_flags('reached_blocks', reached_blocks, n, device)
         _check_block_flags('prior_blocks', prior_blocks, n, device)
-        scratch = (self._scratch_pose if pose else self._scratch_aux if aux else self._scratch)(n, settings, device)
+        scratch = (self._scratch_absgrad if absd is not None else self._scratch_pose if pose else self._scratch_aux if aux else self._scratch)(n, settings, device)
         st = _lib.ForwardState(*state)
         args = (_ptr(grad_image), _ptr(image), _ptr(grad_alpha), _ptr(grad_depth), _ptr(depth), _ptr(means), _ptr(scales),
                 _ptr(rotations), _ptr(opacities), _ptr(sh_rest), _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]),
                 _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]), _ptr(grads[4]), _ptr(grads[5]),
                 _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks), _ptr(prior_blocks))
+        if absd is not None:
+            self._check(self.lib.fgs_backward_absgrad(*args, _ptr(absd), _stream_of(device)), 'fgs_backward_absgrad')
+            return grads + (None, None)
         if camera is None:
             self._check(self.lib.fgs_backward_recycled(*args, _stream_of(device)), 'fgs_backward_aux' if aux else 'fgs_backward')
             return grads + (None, None)

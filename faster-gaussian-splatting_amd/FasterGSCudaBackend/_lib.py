@@ -59,6 +59,8 @@ _SIGNATURES = {
     'fgs_backward_recycled': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P, _P, _P]),
     'fgs_backward_pose_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),
     'fgs_backward_pose': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P, _P, _P, _P, _P]),
+    'fgs_backward_absgrad_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),
+    'fgs_backward_absgrad': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P, _P, _P, _P]),
     'fgs_blend_features': (C.c_int32, [_P, _I32, _P, _P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P]),
     'fgs_backward_features': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P,
                                           _P, _I32, _P, _P, _P, _I32, _P]),

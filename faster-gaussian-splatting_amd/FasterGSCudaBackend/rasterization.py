@@ -463,6 +463,65 @@ def diff_rasterize_aux(means: torch.Tensor, scales: torch.Tensor, rotations: tor
     return image, (a if alpha else None), (d if depth else None)
 
 
+class _RasterizeAbsgrad(torch.autograd.Function):
+    """_RasterizeAux whose backward pass also accumulates the absolute-gradient densification statistic into `abs_densification_info`
+    (fgs_backward_absgrad). The maps are optional: without them the forward pass is the plain one. Always synchronous, gradients in fresh tensors."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, abs_densification_info,
+                rasterizer_settings: RasterizerSettings, alpha: bool, depth: bool):
+        _require_gpu(means)
+        params = (means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest)
+        be = default_backend()
+        if alpha or depth:
+            res = be.forward_aux(*params, rasterizer_settings, alpha, depth)
+            res_alpha, res_depth = res.alpha, res.depth
+        else:
+            res = be.forward(*params, rasterizer_settings)
+            res_alpha = res_depth = None
+        ctx.rasterizer_settings = rasterizer_settings
+        ctx.buffer_state = res.state
+        ctx.has_depth = res_depth is not None
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None (= zero), not as a tensor of zeros
+        shape = (rasterizer_settings.height, rasterizer_settings.width)
+        a = res_alpha if res_alpha is not None else means.new_empty(shape)            # autograd wants tensors: the placeholders are non-differentiable
+        d = res_depth if res_depth is not None else means.new_empty(shape)
+        ctx.save_for_backward(res.image, d, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.abs_densification_info = abs_densification_info
+        ctx.mark_non_differentiable(densification_info, abs_densification_info, *([a] if res_alpha is None else []), *([d] if res_depth is None else []))
+        return res.image, a, d
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_alpha, grad_depth):
+        image, depth, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        if not ctx.has_depth:
+            grad_depth = None
+        clear_live_blocks([means])
+        grads = default_backend().backward_absgrad(ctx.densification_info, ctx.abs_densification_info, grad_image.contiguous(),
+                                                   grad_alpha.contiguous() if grad_alpha is not None else None,
+                                                   grad_depth.contiguous() if grad_depth is not None else None,
+                                                   image, depth, means, scales, rotations, opacities, sh_rest, buffers, ctx.rasterizer_settings, ctx.buffer_state)
+        return (*grads, None, None, None, None, None)
+
+
+def diff_rasterize_absgrad(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                           sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                           rasterizer_settings: RasterizerSettings, abs_densification_info: torch.Tensor, alpha: bool = False, depth: bool = False):
+    """Training render whose backward pass also accumulates the absolute-gradient densification statistic (AbsGS; gsplat's absgrad=True):
+    (image [3,H,W], alpha [H,W] or None, depth [H,W] or None), the maps as in diff_rasterize_aux. `abs_densification_info`: float32 [2,N] like
+    `densification_info`, updated in backward -- row 0 += 1 per visible Gaussian, row 1 += sqrt((0.5 W sum_p |gx_p|)^2 + (0.5 H sum_p |gy_p|)^2) with
+    (gx_p, gy_p) pixel p's share of dL/dmean2d: where densification_info[1] takes the norm of the signed sums, which cancel over a large footprint, this
+    sums magnitudes. A drop-in statistic for adaptive density control (with a threshold of its own). torch.empty(0) for it gives diff_rasterize_aux
+    (or, without maps, diff_rasterize's gradients). `densification_info` may be updated as well, or be torch.empty(0)."""
+    image, a, d = _RasterizeAbsgrad.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                                          abs_densification_info, rasterizer_settings, bool(alpha), bool(depth))
+    return image, (a if alpha else None), (d if depth else None)
+
+
 class _RasterizePose(torch.autograd.Function):
     """_RasterizeAux whose camera is an input: w2c ([3,4] or [4,4]) and cam_position ([3]) replace the tensors of the settings and receive gradients
     (fgs_backward_pose). The maps are optional: without them the forward pass is the plain one. Always synchronous, gradients in fresh tensors."""

@@ -213,7 +213,8 @@ int forward_tail(const ForwardRequest& rq, PrimitiveBuffers& pb, const TileBuffe
     return FGS_OK;
 }
 
-int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth) {
+int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth,
+                  bool with_abs) {
     if (int rc = check_settings(settings)) return rc;
     if (!state || n_primitives < 0) return fail(FGS_ERR_INVALID_ARGUMENT, "bad state / n_primitives");
     if (static_cast<uint64_t>(n_primitives) * kAccRecordWords + PrimitiveBuffers::kHotFloats > 0xfffffff0ull)      // K11 addresses the accumulator records by 32-bit float offsets
@@ -227,7 +228,7 @@ int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primiti
     P.tb = TileBuffers::carve(tc, P.geo.n_tiles, true);
     P.ib = InstanceBuffers::carve(ic, static_cast<uint32_t>(state->n_instances), P.geo.key_bytes, P.geo.end_bit);
     P.bb = BucketBuffers::carve(bc, static_cast<uint32_t>(state->n_buckets), (state->selector & kStateDepthCheckpoints) != 0);
-    P.sc = BackwardScratch::carve(sc, static_cast<uint32_t>(n_primitives), P.geo.n_tiles, with_depth);
+    P.sc = BackwardScratch::carve(sc, static_cast<uint32_t>(n_primitives), P.geo.n_tiles, with_depth, with_abs);
     return FGS_OK;
 }
 
@@ -263,17 +264,40 @@ int run_blend_backward(const BackwardPlan& P, const float* grad_image, const flo
     return FGS_OK;
 }
 
+static BlendDepthPart blend_depth_part(const BackwardPlan& P, const float* grad_alpha, const float* grad_depth, const float* depth, const float* means) {
+    BlendDepthPart d{};
+    d.grad_alpha = grad_alpha; d.grad_depth = grad_depth; d.depth = depth;
+    d.ckpt_d = grad_depth ? P.bb.ckpt_d : nullptr;
+    d.pixaux = P.sc.pixaux; d.means = means; d.w2c = P.settings->w2c;
+    d.acc_z = P.sc.acc_z; d.acc_z_hot = P.sc.acc_z_hot;
+    d.clear_z_f4 = static_cast<uint32_t>(static_cast<size_t>(reinterpret_cast<char*>(P.sc.acc_z_hot + BackwardScratch::kHotDepthFloats) - reinterpret_cast<char*>(P.sc.acc_z)) / 16);
+    return d;
+}
+
 int run_blend_backward_aux(const BackwardPlan& P, const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth,
                            const float* depth, const float* means, hipStream_t stream) {
-    BlendBackwardDepthArgs a{};
-    a.blend = blend_backward_args(P, grad_image, image, true);
-    a.d.grad_alpha = grad_alpha; a.d.grad_depth = grad_depth; a.d.depth = depth;
-    a.d.ckpt_d = grad_depth ? P.bb.ckpt_d : nullptr;
-    a.d.pixaux = P.sc.pixaux; a.d.means = means; a.d.w2c = P.settings->w2c;
-    a.d.acc_z = P.sc.acc_z; a.d.acc_z_hot = P.sc.acc_z_hot;
-    a.d.clear_z_f4 = static_cast<uint32_t>(static_cast<size_t>(reinterpret_cast<char*>(P.sc.acc_z_hot + BackwardScratch::kHotDepthFloats) - reinterpret_cast<char*>(P.sc.acc_z)) / 16);
+    const BlendBackwardDepthArgs a{blend_backward_args(P, grad_image, image, true), blend_depth_part(P, grad_alpha, grad_depth, depth, means)};
     { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels_depth(a, stream)); }
     { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward_depth(a, stream)); }
+    return FGS_OK;
+}
+
+int run_blend_backward_abs(const BackwardPlan& P, const float* grad_image, const float* image, bool with_maps, const float* grad_alpha, const float* grad_depth,
+                           const float* depth, const float* means, hipStream_t stream) {
+    static_assert(BackwardScratch::kHotAbsFloats % 4 == 0, "the cleared region is a whole number of 16-byte pieces");
+    BlendAbsPart y{};
+    y.acc_abs = P.sc.acc_abs; y.acc_abs_hot = P.sc.acc_abs_hot;      // 2 n + the replicas < 2^32 floats: n <= 477 M (plan_backward)
+    y.clear_abs_f4 = static_cast<uint32_t>(static_cast<size_t>(reinterpret_cast<char*>(P.sc.acc_abs_hot + BackwardScratch::kHotAbsFloats) - reinterpret_cast<char*>(P.sc.acc_abs)) / 16);
+    const BlendBackwardArgs blend = blend_backward_args(P, grad_image, image, true);
+    if (with_maps) {
+        const BlendBackwardDepthAbsArgs a{blend, blend_depth_part(P, grad_alpha, grad_depth, depth, means), y};
+        { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels_depth_abs(a, stream)); }
+        { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward_depth_abs(a, stream)); }
+    } else {
+        const BlendBackwardAbsArgs a{blend, y};
+        { StageScope t(ST_STAGE_PIXELS, stream); FGS_HIP(launch_stage_pixels_abs(a, stream)); }
+        { StageScope t(ST_BLEND_BACKWARD, stream); FGS_HIP(launch_blend_backward_abs(a, stream)); }
+    }
     return FGS_OK;
 }
 
@@ -408,6 +432,13 @@ size_t fgs_backward_aux_scratch_bytes(int32_t n_primitives, int32_t width, int32
     return c.total();
 }
 
+size_t fgs_backward_absgrad_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height) {
+    if (n_primitives < 0 || width <= 0 || height <= 0) return 0;
+    Carver c(nullptr);
+    BackwardScratch::carve(c, static_cast<uint32_t>(n_primitives), geometry_of(width, height).n_tiles, true, true);
+    return c.total();
+}
+
 int32_t fgs_backward_live(const float* grad_image, const float* image,
                           const float* means, const float* scales, const float* rotations, const float* opacities,
                           const float* sh_coefficients_rest,
@@ -490,16 +521,27 @@ static int backward_pass(const float* grad_image, const float* image, const floa
                          float* densification_info, void* scratch,
                          int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                          uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, const FeatureGradient* feat,
-                         void* stream_) {
+                         float* abs_densification_info, void* stream_) {
     const bool with_pose = grad_w2c != nullptr || grad_cam_position != nullptr;
+    const bool with_abs = abs_densification_info != nullptr;
     if (prior_blocks != nullptr && reached_blocks == nullptr)
         return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks without reached_blocks: the caller could not make the promise again for the next pass");
     if (prior_blocks != nullptr && (prior_blocks == reached_blocks || prior_blocks == live_blocks))
         return fail(FGS_ERR_INVALID_ARGUMENT, "prior_blocks aliases %s: the pass reads the one while it writes the other", prior_blocks == reached_blocks ? "reached_blocks" : "live_blocks");
     const bool with_maps = grad_alpha != nullptr || grad_depth != nullptr;
     BackwardPlan P;
-    if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state, with_maps)) return rc;
+    if (int rc = plan_backward(P, {primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, scratch}, n_primitives, settings, state, with_maps, with_abs)) return rc;
     if (!grad_image || !image) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL image / grad_image");
+    if (with_abs) {
+        if (state->selector & kStateAsyncCounts)
+            return fail(FGS_ERR_INVALID_ARGUMENT, "abs_densification_info needs the buffers of a synchronous forward pass (fgs_forward / fgs_forward_aux), these are fgs_forward_async's");
+        if (state->selector & kStateFromRecords)
+            return fail(FGS_ERR_INVALID_ARGUMENT, "abs_densification_info does not take the sharded / record paths: these buffers were filled from splat records");
+        const uintptr_t lo_a = reinterpret_cast<uintptr_t>(abs_densification_info), lo_d = reinterpret_cast<uintptr_t>(densification_info);
+        const uintptr_t info_bytes = 2 * sizeof(float) * static_cast<uintptr_t>(n_primitives);
+        if (densification_info != nullptr && (lo_a == lo_d || (lo_a < lo_d + info_bytes && lo_d < lo_a + info_bytes)))
+            return fail(FGS_ERR_INVALID_ARGUMENT, "abs_densification_info aliases densification_info: the signed and the absolute statistic are two tensors");
+    }
     if (grad_depth && !(state->selector & kStateDepthCheckpoints))
         return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth needs the depth checkpoints that fgs_forward_aux writes: these buffers were filled by a forward pass without them");
     if (grad_depth && !depth_expected) return fail(FGS_ERR_INVALID_ARGUMENT, "grad_depth without depth_expected (the map fgs_forward_aux returned)");
@@ -513,7 +555,8 @@ static int backward_pass(const float* grad_image, const float* image, const floa
     if (!means || !scales || !rotations || !opacities || !grad_means || !grad_scales || !grad_rotations || !grad_opacities || !grad_sh_coefficients_0)
         return fail(FGS_ERR_INVALID_ARGUMENT, "NULL parameter / gradient tensor");
     if (with_pose && !g_fused_single_kernel) return fail(FGS_ERR_INVALID_ARGUMENT, "pose gradients are reduced by the one-kernel K12 only (dev option: the two-kernel form is selected)");
-    if (with_maps) { if (int rc = run_blend_backward_aux(P, grad_image, image, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
+    if (with_abs) { if (int rc = run_blend_backward_abs(P, grad_image, image, with_maps, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
+    else if (with_maps) { if (int rc = run_blend_backward_aux(P, grad_image, image, grad_alpha, grad_depth, depth_expected, means, stream)) return rc; }
     else if (int rc = run_blend_backward(P, grad_image, image, stream)) return rc;
     // behind K11's last kernel (the hot replicas are folded, the records are marked dirty), in front of K12: the feature term adds into the same records
     if (feat) { if (int rc = run_blend_features_backward(P, *feat, stream)) return rc; }
@@ -547,7 +590,27 @@ static int backward_pass(const float* grad_image, const float* image, const floa
     }
     // z_i's own dependence on mean_i: grad_means += dL/dz w2c[2, 0:3], after K12 has written every element. Not launched without a depth gradient.
     if (grad_depth) { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_depth_mean_gradient(P.sc.acc_z, P.pb.n_touched, settings->w2c, grad_means, static_cast<uint32_t>(n_primitives), stream)); }
+    // the absolute-gradient statistic, from K11's two extra sums: never enters K12, so either form of it above serves
+    if (with_abs) { StageScope t(ST_PREPROCESS_BACKWARD, stream); FGS_HIP(launch_abs_densification(P.sc.acc_abs, P.pb.n_touched, abs_densification_info, static_cast<uint32_t>(n_primitives),
+                                                                                                    static_cast<float>(settings->width), static_cast<float>(settings->height), stream)); }
     return FGS_OK;
+}
+
+// fgs_backward_recycled that also accumulates the absolute-gradient densification statistic (AbsGS; include/fgs_hip.h): K11 with two more per-Gaussian sums,
+// one small kernel behind K12. abs_densification_info == NULL is fgs_backward_recycled exactly: the same kernels, the plain or the aux scratch layout.
+int32_t fgs_backward_absgrad(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                             const float* means, const float* scales, const float* rotations, const float* opacities,
+                             const float* sh_coefficients_rest,
+                             void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                             float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                             float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                             float* densification_info, void* scratch,
+                             int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                             uint8_t* reached_blocks, const uint8_t* prior_blocks, float* abs_densification_info, void* stream_) {
+    return backward_pass(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
+                         primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
+                         grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
+                         reached_blocks, prior_blocks, nullptr, nullptr, nullptr, abs_densification_info, stream_);
 }
 
 // fgs_backward_recycled that also reduces, inside K12, what the per-Gaussian chains say about the camera: dL/dw2c (rows 0..2) and dL/dcam_position.
@@ -565,7 +628,7 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
     return backward_pass(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
                          primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
                          grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
-                         reached_blocks, prior_blocks, grad_w2c, grad_cam_position, nullptr, stream_);
+                         reached_blocks, prior_blocks, grad_w2c, grad_cam_position, nullptr, nullptr, stream_);
 }
 
 // fgs_backward_reached with the upstream gradient of a feature map of fgs_blend_features: K11 as always, then the feature backward blend -- grad_features
@@ -585,7 +648,7 @@ int32_t fgs_backward_features(const float* grad_image, const float* image, const
     return backward_pass(grad_image, image, grad_alpha, grad_depth, depth_expected, means, scales, rotations, opacities, sh_coefficients_rest,
                          primitive_buffers, tile_buffers, instance_buffers, bucket_buffers, grad_means, grad_scales, grad_rotations, grad_opacities,
                          grad_sh_coefficients_0, grad_sh_coefficients_rest, densification_info, scratch, n_primitives, settings, state, live_blocks,
-                         reached_blocks, nullptr, nullptr, nullptr, grad_feature_map ? &feat : nullptr, stream_);
+                         reached_blocks, nullptr, nullptr, nullptr, grad_feature_map ? &feat : nullptr, nullptr, stream_);
 }
 
 // The F-channel blend over the buffers of a completed synchronous training forward pass (fgs_forward / fgs_forward_aux): feature_map [F,H,W].

@@ -30,15 +30,27 @@ namespace fgs {
 // DEPTH (stage_pixels_kernel<true>, fgs_backward_aux): additionally stages (gD, gA, D_final, T_final) per pixel -- the upstream gradients of expected
 // depth and accumulated opacity and what K11 needs to enlarge the remaining-colour scalar by gD (D_final - D_ckpt) + gA (T_ckpt - T_final) -- and
 // clears acc_z and its hot replicas. Every DEPTH statement is under `if constexpr`: stage_pixels_kernel<false> compiles to the instructions the kernel had.
-template <bool DEPTH> using BackwardArgsOf = std::conditional_t<DEPTH, BlendBackwardDepthArgs, BlendBackwardArgs>;
+// ABS (stage_pixels_kernel<*, true>, fgs_backward_absgrad): additionally clears acc_abs and its hot replicas. Every ABS statement is under `if constexpr`
+// too, and the ABS = false argument types are the ones above: the two ABS = false instantiations compile to the instructions they had.
+template <bool DEPTH, bool ABS = false> using BackwardArgsOf = std::conditional_t<ABS, std::conditional_t<DEPTH, BlendBackwardDepthAbsArgs, BlendBackwardAbsArgs>,
+                                                                                   std::conditional_t<DEPTH, BlendBackwardDepthArgs, BlendBackwardArgs>>;
 __device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardArgs& v) { return v; }
 __device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardDepthArgs& v) { return v.blend; }
+__device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardAbsArgs& v) { return v.blend; }
+__device__ __forceinline__ const BlendBackwardArgs& blend_part(const BlendBackwardDepthAbsArgs& v) { return v.blend; }
 __device__ __forceinline__ BlendDepthPart depth_part(const BlendBackwardArgs&) { return BlendDepthPart{}; }          // never read: every use is under `if constexpr (DEPTH)`
 __device__ __forceinline__ const BlendDepthPart& depth_part(const BlendBackwardDepthArgs& v) { return v.d; }
-template <bool DEPTH>
-__global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BackwardArgsOf<DEPTH> args) {
+__device__ __forceinline__ BlendDepthPart depth_part(const BlendBackwardAbsArgs&) { return BlendDepthPart{}; }
+__device__ __forceinline__ const BlendDepthPart& depth_part(const BlendBackwardDepthAbsArgs& v) { return v.d; }
+__device__ __forceinline__ BlendAbsPart abs_part(const BlendBackwardArgs&) { return BlendAbsPart{}; }               // never read: every use is under `if constexpr (ABS)`
+__device__ __forceinline__ BlendAbsPart abs_part(const BlendBackwardDepthArgs&) { return BlendAbsPart{}; }
+__device__ __forceinline__ const BlendAbsPart& abs_part(const BlendBackwardAbsArgs& v) { return v.abs; }
+__device__ __forceinline__ const BlendAbsPart& abs_part(const BlendBackwardDepthAbsArgs& v) { return v.abs; }
+template <bool DEPTH, bool ABS>
+__global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const BackwardArgsOf<DEPTH, ABS> args) {
     const BlendBackwardArgs& a = blend_part(args);
     [[maybe_unused]] const BlendDepthPart& x = depth_part(args);       // DEPTH only
+    [[maybe_unused]] const BlendAbsPart& y = abs_part(args);           // ABS only
     // (Round 6, measured and withdrawn: XCD x taking a contiguous band of tiles, so that the two tiles sharing a 128-byte line of the six image planes
     // run under one L2 -- what took 6 % off the loss kernels -- leaves this kernel at 0.040 ms: profiles/r06_ab_stage_pixels_xcd.txt.)
     const unsigned tile = blockIdx.x;
@@ -89,6 +101,12 @@ __global__ void __launch_bounds__(kTilePixels) stage_pixels_kernel(const Backwar
         float4* const z = reinterpret_cast<float4*>(x.acc_z);
         const unsigned per_group = (x.clear_z_f4 + gridDim.x - 1u) / gridDim.x;
         const unsigned first = tile * per_group, last = min(first + per_group, x.clear_z_f4);
+        for (unsigned k = first + local; k < last; k += kTilePixels) z[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if constexpr (ABS) {         // acc_abs and its replicas likewise start every pass that sums them at zero
+        float4* const z = reinterpret_cast<float4*>(y.acc_abs);
+        const unsigned per_group = (y.clear_abs_f4 + gridDim.x - 1u) / gridDim.x;
+        const unsigned first = tile * per_group, last = min(first + per_group, y.clear_abs_f4);
         for (unsigned k = first + local; k < last; k += kTilePixels) z[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
 }
@@ -161,10 +179,16 @@ constexpr unsigned kCompactWaves = FGS_K11_WAVES_PER_GROUP;      // independent 
 // gD and gA ride in the pixel-centre ring, which becomes a 16-byte ring (x, y, gD, gA) read with one ds_read_b128 like the dL/dC ring:
 // [xy ring 4 KB | inj 1.5 KB | pix ring 4 KB] = 9 728 bytes per wave = eight allocation granules instead of six. Every DEPTH
 // statement is under `if constexpr`, and `a` is the kernel argument itself: blend_backward_compact_kernel<false> compiles to the instructions the kernel had.
-template <bool DEPTH>
-__global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_kernel(const BackwardArgsOf<DEPTH> args) {
+// ABS (blend_backward_compact_kernel<*, true>, fgs_backward_absgrad): the pair's share of dL/dmean2d is gx = 2 (ca t + cb u), gy = 2 (cb t + cc u); the record's
+// words 0 and 1 are their SIGNED sums, factored out of the loop. Their absolute sums cannot be: two more accumulators per lane, a_ax += |ca t + cb u|,
+// a_ay += |cb t + cc u| (the absolute value is a source modifier of the add; no select, no LDS traffic), doubled once at the end. They leave as a [64][2]
+// block through the dead 16-byte ring behind the record block, two atomic instructions per item in which lane l adds word l & 1 of Gaussian
+// 32 k + (l >> 1): 32 line requests per instruction by the line-request model below. With or without DEPTH; every ABS statement is under `if constexpr`.
+template <bool DEPTH, bool ABS>
+__global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_kernel(const BackwardArgsOf<DEPTH, ABS> args) {
     const BlendBackwardArgs& a = blend_part(args);
     [[maybe_unused]] const BlendDepthPart& x = depth_part(args);       // DEPTH only
+    [[maybe_unused]] const BlendAbsPart& y = abs_part(args);           // ABS only
     const unsigned lane = threadIdx.x & 63u, wave_in_group = threadIdx.x >> 6;
     // Per live pixel: (dL/dC rgb, rel_last as a float) in s_pix and the pixel centre (x, y) in s_xy; slot n_px = dead sentinel (rel 0).
     // Until here x | y << 8 | rel << 16 were packed in the fourth float: three v_cvt_f32_ubyte (4.3 cycles each, tools/valu_rate.hip) and two
@@ -298,6 +322,7 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
         float a_xx = 0.0f, a_xy = 0.0f, a_yy = 0.0f;                  // sum hh dx^2, hh dx dy, hh dy^2   (kb:443-448)
         float sT = 0.0f, sS = 0.0f;                                   // the pixel state travelling through the lanes
         [[maybe_unused]] float a_z = 0.0f;                            // DEPTH: sum w gD = dL/dz
+        [[maybe_unused]] float a_ax = 0.0f, a_ay = 0.0f;              // ABS: sum |ca t + cb u|, sum |cb t + cc u|
 
         // One pipeline step. `inj` / `px`: what this lane read for THIS step (software pipelined: the reads of the following step
         // are issued first). Contributions are made under the lane mask of `contrib` (EXEC), not by selects: a v_cndmask costs
@@ -344,6 +369,7 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
                 const float t = hh * dx, u = hh * dy;
                 a_h += hh; a_x += t; a_y += u;
                 a_xx += t * dx; a_xy += t * dy; a_yy += u * dy;
+                if constexpr (ABS) { a_ax += fabsf(ca * t + cb * u); a_ay += fabsf(cb * t + cc * u); }
                 sT = T * oma;
             }
         };
@@ -388,6 +414,17 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
             mine[0] = v0; mine[1] = v1; mine[2] = a_xx; mine[3] = a_xy; mine[4] = a_yy; mine[5] = v5;
             mine[6] = a_c0 * f0; mine[7] = a_c1 * f1; mine[8] = a_c2 * f2;
             s_off[lane] = adds ? rec_off : kNoRecord;
+            [[maybe_unused]] float* const s_ab = s_t + kBucket * kAccRecordWords;               // ABS: [64][2] behind the record block (2 304 + 512 of the ring's 4 096 bytes)
+            [[maybe_unused]] uint32_t* const s_aoff = s_off + kBucket;                           // ABS: float offset of each lane's pair from acc_abs, or "nothing to add"
+            if constexpr (ABS) {
+                static_assert((kBucket * (kAccRecordWords + 2)) * 4u <= kPixBytes && 2u * kBucket * 4u <= kXyBytes, "both blocks fit the dead rings");
+                const float ax = 2.0f * a_ax, ay = 2.0f * a_ay;
+                s_ab[2u * lane] = ax; s_ab[2u * lane + 1u] = ay;
+                // the Gaussian's own pair, or -- a hot Gaussian -- the pair of its slot in the tile's replica (acc_abs_hot follows acc_abs in the scratch blob)
+                const uint32_t abs_off = hot_word != 0u ? static_cast<uint32_t>(y.acc_abs_hot - y.acc_abs) + ((tile % kHotReplicas) * kMaxHot + (hot_word - 1u)) * 2u
+                                                        : prim * 2u;
+                s_aoff[lane] = (valid_prim && (ax != 0.0f || ay != 0.0f)) ? abs_off : kNoRecord;
+            }
             wave_lds_fence();
             const unsigned sub = lane / kAccRecordWords, comp = lane - sub * kAccRecordWords;     // lane 63 idles: 7 records of 9 words per instruction
 #pragma unroll
@@ -401,6 +438,14 @@ __global__ void __launch_bounds__(kWave * kCompactWaves) blend_backward_compact_
             if constexpr (DEPTH) {        // dL/dz leaves on its own: one float per lane that has something to add
                 if (valid_prim && a_z != 0.0f)
                     unsafeAtomicAdd(hot_word != 0u ? x.acc_z_hot + ((size_t)(tile % kHotReplicas) * kMaxHot + (hot_word - 1u)) : x.acc_z + prim, a_z);
+            }
+            if constexpr (ABS) {          // the two absolute sums: 32 Gaussians per instruction, a Gaussian's two words in neighbouring lanes (one line)
+#pragma unroll
+                for (unsigned k = 0; k < 2u; ++k) {
+                    const unsigned gsn = 32u * k + (lane >> 1);
+                    const uint32_t off = s_aoff[gsn];
+                    if (off != kNoRecord) unsafeAtomicAdd(y.acc_abs + (size_t)off + (lane & 1u), s_ab[2u * gsn + (lane & 1u)]);
+                }
             }
         }
         FGS_K11_PROBE_ITEM_END(lane, item, n_steps);
@@ -432,6 +477,17 @@ __global__ void __launch_bounds__(256) fold_hot_depth_kernel(const BlendBackward
     for (unsigned r = 0; r < kHotReplicas; ++r) sum += a.d.acc_z_hot[(size_t)r * kMaxHot + slot];
     if (sum != 0.0f) a.d.acc_z[a.blend.hot_list[slot]] += sum;                          // one slot per primitive: no other writer at this point
 }
+// the same for the absolute sums of an absgrad backward pass: one thread per (hot slot, word)
+__global__ void __launch_bounds__(256) fold_hot_abs_kernel(const BlendAbsPart y, const uint32_t* __restrict__ hot_list, const uint32_t* __restrict__ hot_count) {
+    const unsigned n_hot = min(*hot_count, kMaxHot);
+    const unsigned e = blockIdx.x * 256u + threadIdx.x;
+    const unsigned slot = e >> 1, k = e & 1u;
+    if (slot >= n_hot) return;
+    float sum = 0.0f;
+#pragma unroll
+    for (unsigned r = 0; r < kHotReplicas; ++r) sum += y.acc_abs_hot[((size_t)r * kMaxHot + slot) * 2u + k];
+    if (sum != 0.0f) y.acc_abs[(size_t)hot_list[slot] * 2u + k] += sum;                 // one slot per primitive: no other writer at this point
+}
 // after K12 (which has written every element of grad_means): z_i = w2c[2, 0:3] . mean_i + w2c[2, 3], so dL/dmean_i += dL/dz_i w2c[2, 0:3]
 __global__ void __launch_bounds__(256) depth_mean_gradient_kernel(const float* __restrict__ acc_z, const uint32_t* __restrict__ n_touched,
                                                                   const float* __restrict__ w2c, float* __restrict__ grad_means, const uint32_t n) {
@@ -440,6 +496,20 @@ __global__ void __launch_bounds__(256) depth_mean_gradient_kernel(const float* _
     const float g = acc_z[i];
     if (g == 0.0f) return;
     grad_means[3 * (size_t)i] += g * w2c[8]; grad_means[3 * (size_t)i + 1] += g * w2c[9]; grad_means[3 * (size_t)i + 2] += g * w2c[10];
+}
+
+// after K12, which is not touched: the absolute-gradient densification statistic of the visible Gaussians, in the arithmetic of the signed one
+// (preprocess_backward.hip, kb:194-201). Unreached visible Gaussians count in row 0; += sqrt(0) on row 1 is exact and omitted.
+__global__ void __launch_bounds__(256) abs_densification_kernel(const float* __restrict__ acc_abs, const uint32_t* __restrict__ n_touched,
+                                                                float* __restrict__ info, const uint32_t n, const float width, const float height) {
+#pragma clang fp contract(off)          // nx nx + ny ny rounds as in K12, whose unit is built without contraction
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || n_touched[i] == 0u) return;
+    info[i] += 1.0f;
+    const float ax = acc_abs[2 * (size_t)i], ay = acc_abs[2 * (size_t)i + 1];
+    if (ax == 0.0f && ay == 0.0f) return;
+    const float nx = 0.5f * (ax * width), ny = 0.5f * (ay * height);
+    info[n + i] += sqrtf(nx * nx + ny * ny);
 }
 
 #ifdef FGS_DEV_SWITCHES
@@ -457,7 +527,7 @@ hipError_t launch_stage_pixels(const BlendBackwardArgs& a_in, hipStream_t s) {
     BlendBackwardArgs a = a_in;
     if (a.variant >= 3 && a.n_buckets_cap != 0) hipLaunchKernelGGL(plan_blend_backward_kernel, dim3(1), dim3(kTileScanThreads), 0, s, a);
     else a.live_offsets = nullptr;                            // the other variants walk all buckets: no list
-    hipLaunchKernelGGL(stage_pixels_kernel<false>, dim3(a.n_tiles), dim3(kTilePixels), 0, s, a);
+    hipLaunchKernelGGL((stage_pixels_kernel<false, false>), dim3(a.n_tiles), dim3(kTilePixels), 0, s, a);
     return hipGetLastError();
 }
 
@@ -476,7 +546,7 @@ hipError_t launch_blend_backward(const BlendBackwardArgs& a_in, hipStream_t s) {
     // grid-stride over the live list: at most 64 Ki single-wave workgroups, so a scene with few live buckets does not pay
     // for the launch of a quarter of a million empty ones
     const unsigned blocks = a.n_buckets_cap < kBackwardMaxBlocks ? a.n_buckets_cap : kBackwardMaxBlocks;
-    hipLaunchKernelGGL(blend_backward_compact_kernel<false>, dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
+    hipLaunchKernelGGL((blend_backward_compact_kernel<false, false>), dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
     hipLaunchKernelGGL(fold_hot_accumulators_kernel, dim3(9u * kMaxHot / 256u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -487,7 +557,7 @@ hipError_t launch_stage_pixels_depth(const BlendBackwardDepthArgs& a_in, hipStre
     a.blend.variant = 3;
     if (a.blend.n_buckets_cap != 0) hipLaunchKernelGGL(plan_blend_backward_kernel, dim3(1), dim3(kTileScanThreads), 0, s, a.blend);
     else a.blend.live_offsets = nullptr;
-    hipLaunchKernelGGL(stage_pixels_kernel<true>, dim3(a.blend.n_tiles), dim3(kTilePixels), 0, s, a);
+    hipLaunchKernelGGL((stage_pixels_kernel<true, false>), dim3(a.blend.n_tiles), dim3(kTilePixels), 0, s, a);
     return hipGetLastError();
 }
 
@@ -496,9 +566,42 @@ hipError_t launch_blend_backward_depth(const BlendBackwardDepthArgs& a_in, hipSt
     BlendBackwardDepthArgs a = a_in;
     a.blend.variant = 3; a.blend.ablate = 0;
     const unsigned blocks = a.blend.n_buckets_cap < kBackwardMaxBlocks ? a.blend.n_buckets_cap : kBackwardMaxBlocks;
-    hipLaunchKernelGGL(blend_backward_compact_kernel<true>, dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
+    hipLaunchKernelGGL((blend_backward_compact_kernel<true, false>), dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
     hipLaunchKernelGGL(fold_hot_accumulators_kernel, dim3(9u * kMaxHot / 256u), dim3(256), 0, s, a.blend);
     hipLaunchKernelGGL(fold_hot_depth_kernel, dim3(kMaxHot / 256u), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// The absgrad forms, without and with map gradients: the product formulation like the depth forms
+template <class Args, bool DEPTH>
+static hipError_t stage_pixels_abs(const Args& a_in, hipStream_t s) {
+    Args a = a_in;
+    a.blend.variant = 3;
+    if (a.blend.n_buckets_cap != 0) hipLaunchKernelGGL(plan_blend_backward_kernel, dim3(1), dim3(kTileScanThreads), 0, s, a.blend);
+    else a.blend.live_offsets = nullptr;
+    hipLaunchKernelGGL((stage_pixels_kernel<DEPTH, true>), dim3(a.blend.n_tiles), dim3(kTilePixels), 0, s, a);
+    return hipGetLastError();
+}
+template <class Args, bool DEPTH>
+static hipError_t blend_backward_abs(const Args& a_in, hipStream_t s) {
+    if (a_in.blend.n_buckets_cap == 0) return hipSuccess;
+    Args a = a_in;
+    a.blend.variant = 3; a.blend.ablate = 0;
+    const unsigned blocks = a.blend.n_buckets_cap < kBackwardMaxBlocks ? a.blend.n_buckets_cap : kBackwardMaxBlocks;
+    hipLaunchKernelGGL((blend_backward_compact_kernel<DEPTH, true>), dim3((blocks + kCompactWaves - 1) / kCompactWaves), dim3(kWave * kCompactWaves), 0, s, a);
+    hipLaunchKernelGGL(fold_hot_accumulators_kernel, dim3(9u * kMaxHot / 256u), dim3(256), 0, s, a.blend);
+    if constexpr (DEPTH) hipLaunchKernelGGL(fold_hot_depth_kernel, dim3(kMaxHot / 256u), dim3(256), 0, s, BlendBackwardDepthArgs{a.blend, a.d});
+    hipLaunchKernelGGL(fold_hot_abs_kernel, dim3(2u * kMaxHot / 256u), dim3(256), 0, s, a.abs, a.blend.hot_list, a.blend.hot_count);
+    return hipGetLastError();
+}
+hipError_t launch_stage_pixels_abs(const BlendBackwardAbsArgs& a, hipStream_t s) { return stage_pixels_abs<BlendBackwardAbsArgs, false>(a, s); }
+hipError_t launch_blend_backward_abs(const BlendBackwardAbsArgs& a, hipStream_t s) { return blend_backward_abs<BlendBackwardAbsArgs, false>(a, s); }
+hipError_t launch_stage_pixels_depth_abs(const BlendBackwardDepthAbsArgs& a, hipStream_t s) { return stage_pixels_abs<BlendBackwardDepthAbsArgs, true>(a, s); }
+hipError_t launch_blend_backward_depth_abs(const BlendBackwardDepthAbsArgs& a, hipStream_t s) { return blend_backward_abs<BlendBackwardDepthAbsArgs, true>(a, s); }
+
+hipError_t launch_abs_densification(const float* acc_abs, const uint32_t* n_touched, float* info, uint32_t n, float width, float height, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(abs_densification_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, acc_abs, n_touched, info, n, width, height);
     return hipGetLastError();
 }
 

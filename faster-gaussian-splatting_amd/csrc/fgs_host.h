@@ -131,15 +131,23 @@ struct BackwardScratch {
     float* view_dir; float4* pixrec;
     // fgs_backward_aux only (behind the plain layout): staged (gD, gA, D_final, T_final) per pixel, dL/dz per Gaussian and the hot Gaussians' replicas of it
     float4* pixaux; float* acc_z; float* acc_z_hot;
+    // fgs_backward_absgrad only (behind the aux layout, whether or not map gradients arrive: both smaller layouts stay prefixes): the absolute sums
+    // (ax, ay) per Gaussian, interleaved, and the hot Gaussians' replicas of them
+    float* acc_abs; float* acc_abs_hot;
     static constexpr size_t kHotDepthFloats = (size_t)kHotReplicas * kMaxHot;
-    static BackwardScratch carve(Carver& c, uint32_t n, uint32_t t, bool with_depth = false) {
+    static constexpr size_t kHotAbsFloats = (size_t)kHotReplicas * kMaxHot * 2;
+    static BackwardScratch carve(Carver& c, uint32_t n, uint32_t t, bool with_depth = false, bool with_abs = false) {
         BackwardScratch b{};
         b.view_dir = c.take<float>("view_dir", (size_t)n * 3);
         b.pixrec = c.take<float4>("pixrec", (size_t)t * kTilePixels * 2);
-        if (with_depth) {
+        if (with_depth || with_abs) {
             b.pixaux = c.take<float4>("pixaux", (size_t)t * kTilePixels);
             b.acc_z = c.take<float>("acc_z", ((size_t)n + 3) / 4 * 4);
             b.acc_z_hot = c.take<float>("acc_z_hot", kHotDepthFloats);
+        }
+        if (with_abs) {
+            b.acc_abs = c.take<float>("acc_abs", ((size_t)n * 2 + 3) / 4 * 4);
+            b.acc_abs_hot = c.take<float>("acc_abs_hot", kHotAbsFloats);
         }
         return b;
     }
@@ -282,10 +290,15 @@ struct BackwardPlan {
     Geometry geo; PrimitiveBuffers pb; TileBuffers tb; InstanceBuffers ib; BucketBuffers bb; BackwardScratch sc;
 };
 // with_depth: the scratch blob has the layout of fgs_backward_aux_scratch_bytes. The bucket blob is carved with ckpt_d whenever the state says it has one.
-int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth = false);
+// with_abs: ... of fgs_backward_absgrad_scratch_bytes (the aux layout with the absolute sums behind it).
+int plan_backward(BackwardPlan& P, const BackwardBlobs& blobs, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, bool with_depth = false,
+                  bool with_abs = false);
 // staging pass + K11. cleared_by_preprocess: a K1 of this library filled the primitive blob and cleared the visible Gaussians' accumulator records
 int run_blend_backward(const BackwardPlan& P, const float* grad_image, const float* image, hipStream_t stream, bool cleared_by_preprocess = true);
 // the same with upstream gradients of accumulated opacity / expected depth (either may be NULL = zero; `depth` = the forward pass's map, read with grad_depth)
 int run_blend_backward_aux(const BackwardPlan& P, const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth,
+                           const float* depth, const float* means, hipStream_t stream);
+// either of the two that also sums the absolute per-pixel shares of dL/dmean2d into P.sc.acc_abs (a plan made with_abs); with_maps: the second form
+int run_blend_backward_abs(const BackwardPlan& P, const float* grad_image, const float* image, bool with_maps, const float* grad_alpha, const float* grad_depth,
                            const float* depth, const float* means, hipStream_t stream);
 }  // namespace fgs

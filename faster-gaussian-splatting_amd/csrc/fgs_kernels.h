@@ -186,6 +186,23 @@ hipError_t launch_stage_pixels_depth(const BlendBackwardDepthArgs& a, hipStream_
 hipError_t launch_blend_backward_depth(const BlendBackwardDepthArgs& a, hipStream_t s);   // always the product formulation (compact), then both folds
 // after K12: grad_means[i] += acc_z[i] * w2c[2, 0:3] for the Gaussians with n_touched != 0 -- all that z_i's own dependence on mean_i contributes
 hipError_t launch_depth_mean_gradient(const float* acc_z, const uint32_t* n_touched, const float* w2c, float* grad_means, uint32_t n, hipStream_t s);
+// K11 that also sums the ABSOLUTE per-pixel shares of dL/dmean2d (fgs_backward_absgrad): ax_i = sum_p |gx_p|, ay_i = sum_p |gy_p| over the pairs that
+// contribute, gx_p = 2 (ca t + cb u), gy_p = 2 (cb t + cc u) -- the terms whose signed sums are words 0 and 1 of the record. Two more per-Gaussian sums
+// that ride along like dL/dz; they travel in a struct of their own behind the plain or the depth arguments, which stay byte for byte what they are.
+struct BlendAbsPart {
+    float* acc_abs;                                      // [N][2] (ax, ay) interleaved, followed by the hot Gaussians' replicas; both cleared by the staging pass
+    float* acc_abs_hot;                                  // [kHotReplicas][kMaxHot][2] (K11 addresses both as 32-bit float offsets from acc_abs)
+    uint32_t clear_abs_f4;                               // 16-byte pieces from acc_abs to the end of acc_abs_hot
+};
+struct BlendBackwardAbsArgs { BlendBackwardArgs blend; BlendAbsPart abs; };
+struct BlendBackwardDepthAbsArgs { BlendBackwardArgs blend; BlendDepthPart d; BlendAbsPart abs; };
+// always the product formulation (compact), then the folds (records, dL/dz with depth arguments, the absolute sums)
+hipError_t launch_stage_pixels_abs(const BlendBackwardAbsArgs& a, hipStream_t s);
+hipError_t launch_blend_backward_abs(const BlendBackwardAbsArgs& a, hipStream_t s);
+hipError_t launch_stage_pixels_depth_abs(const BlendBackwardDepthAbsArgs& a, hipStream_t s);
+hipError_t launch_blend_backward_depth_abs(const BlendBackwardDepthAbsArgs& a, hipStream_t s);
+// after K12: for the Gaussians with n_touched != 0, info[i] += 1 and info[n + i] += sqrt((0.5 W ax_i)^2 + (0.5 H ay_i)^2) (info: float [2][N])
+hipError_t launch_abs_densification(const float* acc_abs, const uint32_t* n_touched, float* info, uint32_t n, float width, float height, hipStream_t s);
 
 // blend_features.hip: F per-Gaussian feature channels blended with the compositing weights of a completed training forward pass (fgs_blend_features),
 // and the backward pass of that blend (fgs_backward_features), which runs between K11 and K12. Both walk the tile lists K10 built, bounded per

@@ -25,6 +25,10 @@ from .trainer import PARAM_ORDER, Gaussians
 GARDEN_SCHEDULE = {  # fastergs_garden.yaml:66-70 / Trainer.py:16-67
     'densification_start': 600, 'densification_end': 14_900, 'densification_interval': 100, 'grad_threshold': 2.0e-4,
     'percent_dense': 0.01, 'opacity_reset_interval': 3_000, 'morton_interval': 5_000, 'morton_end': 15_000, 'sh_interval': 1_000,
+    # 'absgrad': True -- density control reads the absolute-gradient statistic (g.abs_densification_info, accumulated by training_iteration(absgrad=True))
+    # against 'absgrad_threshold' instead of the signed one against 'grad_threshold'. 8e-4 is the value common practice pairs with the absolute
+    # statistic (AbsGS, gsplat's absgrad); it has NOT been validated with this harness.
+    'absgrad': False, 'absgrad_threshold': 8.0e-4,
 }
 
 
@@ -117,6 +121,8 @@ def _gather(g: Gaussians, index: torch.Tensor, be) -> None:
     _adopt(g, outs[:6], outs[6:12] if m else None, outs[12:18] if m else None)
     if g.densification_info is not None:
         g.densification_info = g.densification_info[:, index].contiguous()
+    if getattr(g, 'abs_densification_info', None) is not None:
+        g.abs_densification_info = g.abs_densification_info[:, index].contiguous()
 
 
 def prune(g: Gaussians, prune_mask: torch.Tensor, ops_backend=None) -> None:
@@ -128,6 +134,8 @@ def prune(g: Gaussians, prune_mask: torch.Tensor, ops_backend=None) -> None:
     _rebind(g, {k: getattr(g, k).detach()[keep] for k in PARAM_ORDER}, lambda s, k: s[keep])
     if g.densification_info is not None:
         g.densification_info = g.densification_info[:, keep].contiguous()
+    if getattr(g, 'abs_densification_info', None) is not None:
+        g.abs_densification_info = g.abs_densification_info[:, keep].contiguous()
 
 
 def sort(g: Gaussians, ordering: torch.Tensor, ops_backend=None) -> None:
@@ -138,6 +146,8 @@ def sort(g: Gaussians, ordering: torch.Tensor, ops_backend=None) -> None:
     _rebind(g, {k: getattr(g, k).detach()[ordering] for k in PARAM_ORDER}, lambda s, k: s[ordering])
     if g.densification_info is not None:
         g.densification_info = g.densification_info[:, ordering].contiguous()
+    if getattr(g, 'abs_densification_info', None) is not None:
+        g.abs_densification_info = g.abs_densification_info[:, ordering].contiguous()
 
 
 def apply_morton_ordering(g: Gaussians, ops_backend=None) -> None:
@@ -149,8 +159,11 @@ def apply_morton_ordering(g: Gaussians, ops_backend=None) -> None:
     sort(g, morton_order(g.means.detach().cpu()).to(g.means.device))
 
 
-def reset_densification_info(g: Gaussians) -> None:
+def reset_densification_info(g: Gaussians, absgrad: bool = False) -> None:
+    """absgrad, or a model that carries the absolute statistic: that tensor starts over as well."""
     g.densification_info = torch.zeros((2, g.means.shape[0]), dtype=torch.float32, device=g.means.device)   # Model.py:308-310
+    if absgrad or getattr(g, 'abs_densification_info', None) is not None:
+        g.abs_densification_info = torch.zeros((2, g.means.shape[0]), dtype=torch.float32, device=g.means.device)
 
 
 def reset_opacities(g: Gaussians) -> None:
@@ -162,10 +175,13 @@ def reset_opacities(g: Gaussians) -> None:
 
 
 def adaptive_density_control(g: Gaussians, grad_threshold: float, min_opacity: float, prune_large_gaussians: bool,
-                             percent_dense: float = 0.01, generator: torch.Generator | None = None, ops_backend=None) -> dict:
-    """Model.py:312-366: clone small / split large Gaussians whose mean screen-space gradient exceeds the threshold, then prune."""
+                             percent_dense: float = 0.01, generator: torch.Generator | None = None, ops_backend=None, absgrad: bool = False) -> dict:
+    """Model.py:312-366: clone small / split large Gaussians whose mean screen-space gradient exceeds the threshold, then prune.
+    absgrad: the statistic is g.abs_densification_info (zeros if no pass has accumulated it yet) and `grad_threshold` is the caller's for it."""
     be = _device_backend(g, ops_backend)
     if be is not None:
+        if absgrad and (g.abs_densification_info is None or g.abs_densification_info.shape[1] != g.means.shape[0]):
+            g.abs_densification_info = torch.zeros((2, g.means.shape[0]), dtype=torch.float32, device=g.means.device)
         params = [getattr(g, k).detach() for k in PARAM_ORDER]
         ensure_state(g)
         m, v = _moments(g)
@@ -174,10 +190,11 @@ def adaptive_density_control(g: Gaussians, grad_threshold: float, min_opacity: f
         if generator is not None:      # reproducible runs: the samples come from the given generator (CPU generators feed the device tensor)
             noise_fn = lambda rows: torch.randn((rows, 3), generator=generator, device=generator.device).to(dev)
         new_p, new_m, new_v, (kept, clones, children, split) = be.adaptive_density_control(
-            g.densification_info, params, m, v, grad_threshold, min_opacity, prune_large_gaussians, percent_dense, g.extent, noise_fn)
+            g.abs_densification_info if absgrad else g.densification_info, params, m, v, grad_threshold, min_opacity, prune_large_gaussians, percent_dense, g.extent, noise_fn)
         n_old = params[0].shape[0]
         _adopt(g, new_p, new_m, new_v)
         g.densification_info = None                                                        # Model.py:353-355
+        g.abs_densification_info = None
         # cloned / children_per_copy count what SURVIVED the pruning that follows the densification; pruned = old Gaussians that are gone
         return {'cloned': clones, 'split': split, 'pruned': n_old - kept, 'total': g.means.shape[0], 'kept': kept, 'children_per_copy': children}
     raise RuntimeError('adaptive_density_control: the Gaussians live on the CPU and no backend was given -- density control exists as the device '
@@ -191,9 +208,11 @@ def run_callbacks(g: Gaussians, iteration: int, schedule: dict = GARDEN_SCHEDULE
     if iteration >= s['sh_interval'] and iteration % s['sh_interval'] == 0:
         g.increase_used_sh_degree()
     if s['densification_start'] <= iteration <= s['densification_end'] and (iteration - s['densification_start']) % s['densification_interval'] == 0:
-        out = adaptive_density_control(g, s['grad_threshold'], 0.005, iteration > s['opacity_reset_interval'], s['percent_dense'], generator, ops_backend)
+        absgrad = bool(s.get('absgrad', False))
+        out = adaptive_density_control(g, s['absgrad_threshold'] if absgrad else s['grad_threshold'], 0.005, iteration > s['opacity_reset_interval'],
+                                       s['percent_dense'], generator, ops_backend, absgrad=absgrad)
         if iteration < s['densification_end']:
-            reset_densification_info(g)
+            reset_densification_info(g, absgrad)
     if iteration <= s['morton_end'] and iteration % s['morton_interval'] == 0:
         apply_morton_ordering(g, ops_backend)
     if s['opacity_reset_interval'] <= iteration <= s['densification_end'] and iteration % s['opacity_reset_interval'] == 0:
@@ -254,6 +273,7 @@ def _split_mass(g: Gaussians, sources: torch.Tensor, min_opacity: float, relocat
 def _forget_moments_and_statistics(g: Gaussians, rows: torch.Tensor) -> None:
     reset_state(g, rows)
     g.densification_info = None
+    g.abs_densification_info = None
 
 
 @torch.no_grad()

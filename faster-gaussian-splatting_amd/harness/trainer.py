@@ -13,7 +13,8 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_aux, diff_rasterize_features, rasterize, rasterize_aux
+from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_features, rasterize,
+                                 rasterize_aux)
 
 from .scenes import View
 
@@ -37,6 +38,7 @@ class Gaussians(torch.nn.Module):
         self.max_sh_degree = max_sh_degree
         self.active_sh_degree = max_sh_degree if active_sh_degree is None else active_sh_degree
         self.densification_info = torch.zeros((2, self.means.shape[0]), dtype=torch.float32, device=device)   # Model.py:308-310
+        self.abs_densification_info: 'torch.Tensor | None' = None      # the absolute-gradient statistic [2,N]: made by the first pass that accumulates it
         self.optimizer: FusedAdam | None = None
         self.extent = 1.0
 
@@ -78,6 +80,18 @@ def render_image_training_aux(g: Gaussians, view: View, update_densification_inf
     return diff_rasterize_aux(*g.tensors(),
                               densification_info=g.densification_info if update_densification_info else torch.empty(0),
                               rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), alpha=alpha, depth=depth)
+
+
+def render_image_training_absgrad(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, alpha: bool = False,
+                                  depth: bool = False):
+    """render_image_training_aux whose backward pass accumulates the ABSOLUTE-gradient statistic into g.abs_densification_info (made here, zeroed, if
+    the model has none for its current size) instead of the signed one into g.densification_info, which is left alone: (image, alpha or None,
+    depth or None), the maps only on request."""
+    if update_densification_info and (g.abs_densification_info is None or g.abs_densification_info.shape[1] != g.means.shape[0]):
+        g.abs_densification_info = torch.zeros((2, g.means.shape[0]), dtype=torch.float32, device=g.means.device)
+    return diff_rasterize_absgrad(*g.tensors(), densification_info=torch.empty(0),
+                                  rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color),
+                                  abs_densification_info=g.abs_densification_info if update_densification_info else torch.empty(0), alpha=alpha, depth=depth)
 
 
 def render_image_training_features(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, features: torch.Tensor,
@@ -136,13 +150,20 @@ def _unit_gradient(loss: torch.Tensor) -> torch.Tensor:
 
 def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration: int, *, densification_end: int = 14_900,
                        loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss, depth_target: 'torch.Tensor | None' = None,
-                       depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None) -> torch.Tensor:
+                       depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
-    depth supervision through diff_rasterize_aux. Off by default: the step is then exactly the colour-only one."""
+    depth supervision through diff_rasterize_aux. Off by default: the step is then exactly the colour-only one.
+    absgrad: the densification statistic of the step is the absolute-gradient one (g.abs_densification_info, for a schedule with 'absgrad': True);
+    g.densification_info is then not updated. Gradients and loss are the same either way."""
     g.update_learning_rate(iteration + 1)
-    if depth_target is not None and depth_weight > 0.0:
+    with_depth = depth_target is not None and depth_weight > 0.0
+    if absgrad:
+        image, alpha, depth = render_image_training_absgrad(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color,
+                                                            alpha=with_depth, depth=with_depth)
+        loss = loss_fn(image, target) + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid) if with_depth else loss_fn(image, target)
+    elif with_depth:
         image, alpha, depth = render_image_training_aux(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
         loss = loss_fn(image, target) + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid)
     else:

@@ -190,6 +190,30 @@ int32_t fgs_backward_pose(const float* grad_image, const float* image, const flo
                           float* densification_info, void* scratch,
                           int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                           uint8_t* reached_blocks, const uint8_t* prior_blocks, float* grad_w2c, float* grad_cam_position, void* stream);
+/* fgs_backward_recycled that also accumulates the ABSOLUTE-gradient densification statistic (AbsGS; gsplat's absgrad). For every (pixel p, Gaussian i)
+ * pair the backward blend lets contribute, with hh = -1/2 alpha dL/dalpha, t = hh dx, u = hh dy and the conic (ca, cb, cc), the pair's share of
+ * dL/dmean2d is gx_p = 2 (ca t + cb u), gy_p = 2 (cb t + cc u); densification_info[1] accumulates the norm of their SIGNED sums, which cancel for a
+ * Gaussian that covers many pixels. With ax_i = sum_p |gx_p|, ay_i = sum_p |gy_p| (dL/dalpha includes the alpha and depth terms of map gradients):
+ *     abs_densification_info: fp32 [2, n_primitives], accumulated (+=), never cleared here
+ *       row 0 += 1 for every visible Gaussian (n_touched != 0), exactly as densification_info[0]
+ *       row 1 += sqrt((0.5 W ax_i)^2 + (0.5 H ay_i)^2)
+ * -- a drop-in first argument of fgs_adc_plan; the threshold is the caller's. The two sums are formed inside the backward blend kernel (two more
+ * accumulators per lane; no second walk) and turned into the statistic by one small kernel behind K12. abs_densification_info == NULL IS
+ * fgs_backward_recycled: the same kernels, its scratch size. Otherwise scratch: fgs_backward_absgrad_scratch_bytes(), with or without map gradients
+ * (the plain and the aux layout are prefixes of it). densification_info may be given as well, or NULL. The six gradients, both flag arrays and
+ * densification_info are what fgs_backward_recycled leaves. FGS_ERR_INVALID_ARGUMENT, never ignored: buffers of fgs_forward_async or of the record /
+ * sharded forward passes, abs_densification_info overlapping densification_info. n_primitives == 0 writes nothing. Only this materialised-gradient
+ * pass has the statistic: fgs_backward_adam_fused, the sharded and record paths take none; pose and feature gradients have entry points of their own. */
+size_t fgs_backward_absgrad_scratch_bytes(int32_t n_primitives, int32_t width, int32_t height);
+int32_t fgs_backward_absgrad(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                             const float* means, const float* scales, const float* rotations, const float* opacities,
+                             const float* sh_coefficients_rest,
+                             void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                             float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                             float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                             float* densification_info, void* scratch,
+                             int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                             uint8_t* reached_blocks, const uint8_t* prior_blocks, float* abs_densification_info, void* stream);
 
 /* Feature-channel render of the training pass. features: fp32 [n_primitives, n_channels] contiguous, any sign, 1 <= n_channels <= 64. Over exactly the
  * (pixel, Gaussian) pairs the training blend of the forward pass blended, in its order -- the same sub-tile cull, alpha >= 1/255, T_before >= 1e-4, never
