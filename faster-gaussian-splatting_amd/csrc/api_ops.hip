@@ -36,7 +36,6 @@ int32_t fgs_adam_step_multi_quiet(int32_t n_groups, const float* const* grads, f
     if ((live_blocks != nullptr || quiet_blocks != nullptr) && floats_per_gaussian == nullptr) return fail(FGS_ERR_INVALID_ARGUMENT, "live_blocks / quiet_blocks without floats_per_gaussian");
     AdamArgs a{};
     a.live_blocks = live_blocks;
-    uint32_t blocks = 0;
     int64_t rows = -1;                  // quiet_blocks: the N all groups share
     // the skip rests on "adam_update with g = m = v = 0 is the identity", which holds for eps > 0 (as the float the kernel sees) and finite hyperparameters
     // only (0 / 0 and inf * 0 make the dense kernel write NaN, and the skip must not hide that); without live flags, or with a tensor beyond the kernel's
@@ -62,10 +61,7 @@ int32_t fgs_adam_step_multi_quiet(int32_t n_groups, const float* const* grads, f
         }
         quiet_ok = quiet_ok && g.row_len != 0u && g.h.eps > 0.0f && std::isfinite(g.h.eps) && std::isfinite(g.h.step_size) && std::isfinite(g.h.beta1) &&
                    std::isfinite(g.h.beta2) && std::isfinite(g.h.bc2_sqrt_rcp);
-        g.first_block = blocks;
-        blocks += static_cast<uint32_t>((n_elements[k] + 1023) / 1024);
     }
-    a.total_blocks = blocks;
     if (quiet_ok) a.quiet_blocks = quiet_blocks;
     else if (quiet_blocks != nullptr && rows > 0) FGS_HIP(hipMemsetAsync(quiet_blocks, 0, static_cast<size_t>((rows + 63) / 64), static_cast<hipStream_t>(stream)));
     { StageScope t(ST_ADAM, static_cast<hipStream_t>(stream)); FGS_HIP(launch_adam(a, static_cast<hipStream_t>(stream))); }

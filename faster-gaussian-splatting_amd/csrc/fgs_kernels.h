@@ -89,6 +89,7 @@ FGS_SWITCH(g_adam_nontemporal, 1);                   // same, option 2: non-temp
 FGS_SWITCH(g_adam_unroll, 1);                        // same, option 1: 1, 2 or 4 float4 pieces per thread (plain loads / stores only)
 #endif
 FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
+FGS_SWITCH(g_adam_span, 1);                          // adam.hip, option 15: chunks a workgroup of K13 walks one after the other, 1..32 (above 1: costed and not built, profiles/adam_spans.txt)
 // radix_sort.hip: stable LSD radix sort of (key, uint32) pairs sized for these two sorts
 size_t own_sort_temp_bytes(uint32_t n, int end_bit);
 // Side table carried out of the depth sort's LAST scatter pass (radix_sort.hip): the sort's values start as the input positions (the first pass
@@ -293,7 +294,8 @@ struct AdamGroup { const float* grad; float* param; float* exp_avg; float* exp_a
 // quiet_blocks: [ceil(N / 64)] bytes or nullptr (needs live_blocks and one N for all groups); 1 = every exp_avg / exp_avg_sq element of Gaussians
 // 64 b .. 64 b + 63 in every group == 0.0f. With a zero gradient the update is then the identity on parameter and moments: a 16-byte piece whose
 // blocks are quiet and not live is neither loaded nor stored. The kernel clears the byte of every block it reads a gradient for (1 -> 0, never back).
-struct AdamArgs { AdamGroup g[8]; int n_groups; uint32_t total_blocks; int reverse; const uint8_t* live_blocks; uint8_t* quiet_blocks; };
+// span, first_block and total_blocks are the launcher's: a workgroup owns `span` consecutive chunks (1024 floats per piece a thread holds: 4096 in the product) of one group (launch_adam sets all three)
+struct AdamArgs { AdamGroup g[8]; int n_groups; uint32_t total_blocks; int reverse; const uint8_t* live_blocks; uint8_t* quiet_blocks; uint32_t span; };
 hipError_t launch_adam(const AdamArgs& a, hipStream_t s);   // K13, all groups in one launch
 // quiet_out[b] = 1 iff every moment of block b compares equal to 0.0f in every group (NaN is not zero), else 0: one streaming read of the moments.
 // rows = N; group k is [N, row_len[k]]
