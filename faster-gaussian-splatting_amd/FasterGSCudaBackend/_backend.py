@@ -554,6 +554,64 @@ class Backend:
                                                    _ptr(upstream), grad.data_ptr(), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_backward')
         return grad
 
+    # -- per-view bilateral-grid colour correction (include/fgs_hip.h, csrc/bilagrid.hip) ------------------------------------------
+    @staticmethod
+    def _check_bilagrid(grid: torch.Tensor, image: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None) -> tuple:
+        """(device, (Wg, Hg, L), (W, H)) of a [12, L, Hg, Wg] grid and, if given, a [3,H,W] image (and an upstream gradient of its shape)."""
+        tensors, names = [grid], ['grid']
+        if image is not None:
+            tensors.append(image); names.append('image')
+        if grad_out is not None:
+            tensors.append(grad_out); names.append('grad_out')
+        for t, n in zip(tensors, names):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != grid.device:
+                raise RuntimeError(f"bilagrid: '{n}' must be a contiguous float32 tensor on {grid.device}")
+        if grid.dim() != 4 or grid.shape[0] != 12 or min(grid.shape) < 1:
+            raise RuntimeError(f'bilagrid: grid must be [12, L, Hg, Wg] with every extent >= 1, got {tuple(grid.shape)}')
+        if image is not None and (image.dim() != 3 or image.shape[0] != 3 or image.numel() == 0):
+            raise RuntimeError(f'bilagrid: image must be [3, H, W], got {tuple(image.shape)}')
+        if grad_out is not None and grad_out.shape != image.shape:
+            raise RuntimeError(f'bilagrid: grad_out must have the shape of the image {tuple(image.shape)}, got {tuple(grad_out.shape)}')
+        _, gl, gh, gw = grid.shape
+        return grid.device, (gw, gh, gl), (None if image is None else (image.shape[2], image.shape[1]))
+
+    def _scratch_bilagrid(self, extents: tuple, device: torch.device) -> torch.Tensor:
+        return _empty_bytes(self.lib.fgs_bilagrid_scratch_bytes(*extents), device)
+
+    def bilagrid_staged(self, grid_shape: tuple, width: int, height: int) -> bool:
+        """Whether the slice kernels stage the lattice points under a pixel tile in LDS for a [12, L, Hg, Wg] grid over a W x H image (else: global reads)."""
+        _, gl, gh, gw = grid_shape
+        st = self.lib.fgs_bilagrid_staged(int(gw), int(gh), int(gl), int(width), int(height))
+        if st < 0:
+            self._check(st, 'fgs_bilagrid_staged')
+        return bool(st)
+
+    def bilagrid_slice(self, image: torch.Tensor, grid: torch.Tensor) -> torch.Tensor:
+        """image' = A(x, y, luma) image + b(x, y, luma) with the 3 x 4 matrix sliced out of `grid` per pixel: [3,H,W] -> [3,H,W]."""
+        device, ext, (w, h) = self._check_bilagrid(grid, image)
+        out = torch.empty_like(image)
+        self._check(self.lib.fgs_bilagrid_slice(grid.data_ptr(), *ext, image.data_ptr(), w, h, out.data_ptr(), _stream_of(device)), 'fgs_bilagrid_slice')
+        return out
+
+    def bilagrid_slice_backward(self, image: torch.Tensor, grid: torch.Tensor, grad_out: torch.Tensor, need_grid: bool = True,
+                                need_image: bool = True) -> tuple:
+        """(dL/dgrid or None, dL/dimage or None) for the upstream gradient of bilagrid_slice's output; a gradient that is not needed is not computed."""
+        device, ext, (w, h) = self._check_bilagrid(grid, image, grad_out)
+        grad_grid = torch.empty_like(grid) if need_grid else None
+        grad_image = torch.empty_like(image) if need_image else None
+        scratch = self._scratch_bilagrid(ext, device) if need_grid else None
+        self._check(self.lib.fgs_bilagrid_slice_backward(grid.data_ptr(), *ext, image.data_ptr(), grad_out.data_ptr(), w, h, _ptr(grad_grid), _ptr(grad_image),
+                                                         _ptr(scratch), _stream_of(device)), 'fgs_bilagrid_slice_backward')
+        return grad_grid, grad_image
+
+    def bilagrid_tv(self, grid: torch.Tensor, with_grad: bool = True) -> tuple:
+        """(tv(grid) as a 0-dim device tensor, d tv / d grid or None): the sum over the three axes of the mean squared difference of neighbours."""
+        device, ext, _ = self._check_bilagrid(grid)
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        grad = torch.empty_like(grid) if with_grad else None
+        self._check(self.lib.fgs_bilagrid_tv(grid.data_ptr(), *ext, loss.data_ptr(), _ptr(grad), _stream_of(device)), 'fgs_bilagrid_tv')
+        return loss, grad
+
     # -- Gaussian-sharded multi-GPU path (include/fgs_hip.h, "Gaussian-sharded multi-GPU path") --------------------------------
     def _settings_array(self, views: Sequence[RasterizerSettings], total_sh_rest: int, device: torch.device, keep: list):
         arr = (_lib.Settings * len(views))()

@@ -104,6 +104,11 @@ _SIGNATURES = {
     'fgs_l1_dssim_scratch_bytes': (C.c_size_t, [_I32, _I32]),
     'fgs_l1_dssim_loss': (C.c_int32, [_P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
     'fgs_l1_dssim_backward': (C.c_int32, [_P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
+    'fgs_bilagrid_slice': (C.c_int32, [_P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
+    'fgs_bilagrid_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),
+    'fgs_bilagrid_slice_backward': (C.c_int32, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    'fgs_bilagrid_staged': (C.c_int32, [_I32] * 5),
+    'fgs_bilagrid_tv': (C.c_int32, [_P, _I32, _I32, _I32, _P, _P, _P]),
     'fgs_profile_enable': (C.c_int32, [_I32]),
     'fgs_profile_read': (C.c_int32, [C.POINTER(StageTime), _I32]),
     'fgs_debug_wave_selftest': (C.c_int32, [_P, _P]),

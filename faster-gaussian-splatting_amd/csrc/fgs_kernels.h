@@ -316,6 +316,20 @@ size_t l1_dssim_partials(int width, int height);   // number of floats in LossAr
 hipError_t launch_l1_dssim(const LossArgs& a, hipStream_t s);
 hipError_t launch_l1_dssim_backward(const LossArgs& a, hipStream_t s);   // gradient only, from the maps a forward launch left in d_mu / d_m11 / d_m12
 
+// bilagrid.hip: per-view bilateral-grid colour correction of the rendered image (slice), its gradients, and the grid's total variation
+struct BilagridArgs {
+    const float* grid; int gw, gh, gl;           // [12, L, Hg, Wg]
+    const float* image; int width, height;       // [3,H,W]
+    float* out;                                  // forward: [3,H,W]
+    const float* grad_out; float* grad_image;    // backward: upstream [3,H,W]; dL/dimage or nullptr
+    float* scratch;                              // backward: dL/dgrid channel-last [L, Hg, Wg, 12], zero on the stream; nullptr = dL/dgrid not wanted
+    int vec4;                                    // width % 4 == 0 and every image-shaped tensor 16-byte aligned: rows move as float4
+};
+bool bilagrid_staged(int gw, int gh, int gl, int width, int height);   // the launches stage the grid under a tile in LDS (else they read it from global memory)
+hipError_t launch_bilagrid_slice(const BilagridArgs& a, hipStream_t s);
+hipError_t launch_bilagrid_slice_backward(const BilagridArgs& a, float* grad_grid, hipStream_t s);   // grad_grid [12, L, Hg, Wg] is overwritten (with a.scratch)
+hipError_t launch_bilagrid_tv(const float* grid, int gw, int gh, int gl, float* loss, float* grad_grid, hipStream_t s);
+
 // shard_exchange.hip: record (un)packing either side of the two exchanges of the Gaussian-sharded multi-GPU path
 struct PackRecordsView { const PrimRec* rec; const uint32_t* n_touched; const uint32_t* depth_keys; const uint32_t* prim_idx;
                          const uint32_t* counters; uint32_t* slot; uint32_t* out; uint32_t* counts_out; };

@@ -150,13 +150,19 @@ def _unit_gradient(loss: torch.Tensor) -> torch.Tensor:
 
 def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration: int, *, densification_end: int = 14_900,
                        loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss, depth_target: 'torch.Tensor | None' = None,
-                       depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False) -> torch.Tensor:
+                       depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False,
+                       bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
     depth supervision through diff_rasterize_aux. Off by default: the step is then exactly the colour-only one.
     absgrad: the densification statistic of the step is the absolute-gradient one (g.abs_densification_info, for a schedule with 'absgrad': True);
-    g.densification_info is then not updated. Gradients and loss are the same either way."""
+    g.densification_info is then not updated. Gradients and loss are the same either way.
+    bilagrid (harness.bilagrid.BilateralGrids, after its training_setup) with view_index: the rendered image passes through that view's bilateral grid
+    before loss_fn, tv_weight * the grid's total variation is added to the loss, and the module's optimizer steps behind the Gaussians'. None (the
+    default): the step is exactly the one without."""
+    if bilagrid is not None:
+        loss_fn = bilagrid.corrected(loss_fn, view_index, tv_weight)
     g.update_learning_rate(iteration + 1)
     with_depth = depth_target is not None and depth_weight > 0.0
     if absgrad:
@@ -176,4 +182,15 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
         before_step()
     g.optimizer.step()
     g.optimizer.zero_grad()
+    if bilagrid is not None:
+        bilagrid.optimizer.step()
+        bilagrid.optimizer.zero_grad()
     return loss.detach()
+
+
+def render_image_corrected(g: Gaussians, view: View, grids, view_index: int) -> torch.Tensor:
+    """The inference render of a training view with its photometric correction, in the reference's order (Renderer.py:101-104): rasterize without the
+    clamp -> the view's bilateral grid -> clamp to [0, 1]. [3,H,W]."""
+    with torch.no_grad():
+        image = rasterize(*g.tensors(), rasterizer_settings=extract_settings(view, g.active_sh_bases, view.background_color), to_chw=True, clamp_output=False)
+        return grids(image, view_index).clamp_(0.0, 1.0)

@@ -479,6 +479,28 @@ int32_t fgs_l1_dssim_loss(const float* image, const float* target, int32_t width
 int32_t fgs_l1_dssim_backward(const float* image, const float* target, int32_t width, int32_t height, float lambda_l1, float lambda_dssim,
                               const float* upstream, float* grad_image, const void* scratch, void* stream);
 
+/* ---- Per-view bilateral-grid colour correction between the rasterizer and the loss (csrc/bilagrid.hip; INTEGRATION.md "Bilateral grids") ----
+ * grid: fp32 [12, grid_l, grid_h, grid_w], contiguous, every extent >= 1; channel 4 i + j is entry (i, j) of a 3 x 4 matrix [A | b]. For pixel (px, py)
+ * of image [3, height, width] (any range):  u = (px + 0.5) / width * (grid_w - 1), v = (py + 0.5) / height * (grid_h - 1),
+ * g = clamp(0.299 r + 0.587 g + 0.114 b, 0, 1), z = g * (grid_l - 1), M = trilinear interpolation of grid at (z, v, u) (corner indices clamped to
+ * the grid), out_i = sum_j M[4 i + j] * C_j + M[4 i + 3]  ==  F.grid_sample(grid[None], 2 (x, y, g) - 1, bilinear, align_corners=True, border) followed
+ * by the matrix product. Every call refuses (FGS_ERR_INVALID_ARGUMENT, text in fgs_last_error) a NULL required pointer, a non-positive extent or image
+ * size, a grid of more than 2^31 - 1 floats, and `out` overlapping `image`. No host synchronisation, no allocation; all work on `stream`. */
+int32_t fgs_bilagrid_slice(const float* grid, int32_t grid_w, int32_t grid_h, int32_t grid_l, const float* image, int32_t width, int32_t height,
+                           float* out, void* stream);
+/* Gradients for an upstream grad_out [3,H,W]: grad_grid [12, L, Hg, Wg] (OVERWRITTEN; summed with float atomics: the last bits depend on their order)
+ * and grad_image [3,H,W] (written per pixel: deterministic). The guide carries no gradient where it is clamped. Either may be NULL (it then costs
+ * nothing); both NULL is refused. scratch: fgs_bilagrid_scratch_bytes bytes, 4-byte aligned, required with grad_grid; the call clears it itself. */
+size_t fgs_bilagrid_scratch_bytes(int32_t grid_w, int32_t grid_h, int32_t grid_l);
+int32_t fgs_bilagrid_slice_backward(const float* grid, int32_t grid_w, int32_t grid_h, int32_t grid_l, const float* image, const float* grad_out,
+                                    int32_t width, int32_t height, float* grad_grid, float* grad_image, void* scratch, void* stream);
+/* 1: the two calls above stage the lattice points under each 64 x 16 pixel tile in LDS for this grid and image size; 0: that part exceeds the
+ * kernels' LDS budget somewhere and they read the grid from global memory; negative: fgs_status (non-positive argument). */
+int32_t fgs_bilagrid_staged(int32_t grid_w, int32_t grid_h, int32_t grid_l, int32_t width, int32_t height);
+/* Total variation of one grid, tv = sum over the axes z, y, x of mean((G[next along the axis] - G)^2) over all 12 channels (an axis of extent 1
+ * contributes 0): loss = one DEVICE float, grad_grid [12, L, Hg, Wg] = d tv / dG (overwritten) or NULL. One launch, sums in a fixed order. */
+int32_t fgs_bilagrid_tv(const float* grid, int32_t grid_w, int32_t grid_h, int32_t grid_l, float* loss, float* grad_grid, void* stream);
+
 /* Optional per-stage timing. While enabled (1), every pipeline stage is bracketed by hipEvents recorded on the caller's stream
  * (each event costs a few microseconds of GPU idle time: ~0.2 ms per training iteration with all stages on); enable = 2 + k brackets
  * only stage k (its index in the table fgs_profile_read returns), which leaves a timed loop practically undisturbed;
