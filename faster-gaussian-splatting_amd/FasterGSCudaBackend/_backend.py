@@ -512,46 +512,78 @@ class Backend:
                     'fgs_adam_quiet_scan')
         return out
 
-    def _l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float, lambda_dssim: float, with_grad: bool) -> tuple:
-        """fgs_l1_dssim_loss: (sums = (l1, ssim, loss) formed on the device by the reduce kernel, dloss/dimage or None, the scratch with the derivative maps)."""
+    @staticmethod
+    def _loss_weight(weight, image: torch.Tensor) -> torch.Tensor:
+        """The [H,W] per-pixel weight of the weighted loss as the library takes it: float32, contiguous, on the image's device."""
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 2 or tuple(weight.shape) != tuple(image.shape[1:]):
+            raise RuntimeError(f'l1_dssim: weight must be a [H,W] tensor matching the image ({tuple(image.shape[1:])}), got '
+                               f'{tuple(weight.shape) if isinstance(weight, torch.Tensor) else type(weight).__name__}')
+        if weight.device != image.device:
+            raise RuntimeError(f'l1_dssim: weight lives on {weight.device}, the image on {image.device}')
+        if weight.is_complex():
+            raise RuntimeError('l1_dssim: weight must be real (float, integer or bool)')
+        return weight.to(torch.float32).contiguous()
+
+    def _l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float, lambda_dssim: float, with_grad: bool, weight=None) -> tuple:
+        """fgs_l1_dssim_loss: (sums = (l1, ssim, loss) formed on the device by the reduce kernel, dloss/dimage or None, the scratch with the derivative maps).
+        With a weight: fgs_l1_dssim_weighted_loss, the same triple of the weighted definition."""
         device = self._check_params((image, target), ('image', 'target'))
         if image.dim() != 3 or image.shape[0] != 3 or image.shape != target.shape:
             raise RuntimeError('l1_dssim expects two [3,H,W] tensors')
         _, h, w = image.shape
+        if weight is not None:
+            weight = self._loss_weight(weight, image)
         sums = torch.empty(3, dtype=torch.float32, device=device)
         grad = torch.empty_like(image) if with_grad else None
-        scratch = torch.empty(int(self.lib.fgs_l1_dssim_scratch_bytes(w, h)), dtype=torch.uint8, device=device)
-        self._check(self.lib.fgs_l1_dssim_loss(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
-                                               sums.data_ptr(), _ptr(grad), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_loss')
+        if weight is None:
+            scratch = torch.empty(int(self.lib.fgs_l1_dssim_scratch_bytes(w, h)), dtype=torch.uint8, device=device)
+            self._check(self.lib.fgs_l1_dssim_loss(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
+                                                   sums.data_ptr(), _ptr(grad), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_loss')
+        else:
+            scratch = torch.empty(int(self.lib.fgs_l1_dssim_weighted_scratch_bytes(w, h)), dtype=torch.uint8, device=device)
+            self._check(self.lib.fgs_l1_dssim_weighted_loss(image.data_ptr(), target.data_ptr(), weight.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
+                                                            sums.data_ptr(), _ptr(grad), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_weighted_loss')
         return sums, grad, scratch
 
     def l1_dssim(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2,
-                 with_grad: bool = True):
-        """Fused photometric loss (Loss.py:15-16): returns (loss 0-dim tensor, dloss/dimage or None, (l1, ssim) tensor)."""
-        sums, grad, _ = self._l1_dssim(image, target, lambda_l1, lambda_dssim, with_grad)
+                 with_grad: bool = True, weight: Optional[torch.Tensor] = None):
+        """Fused photometric loss (Loss.py:15-16): returns (loss 0-dim tensor, dloss/dimage or None, (l1, ssim) tensor).
+        `weight`: [H,W] per-pixel weights (masks, confidences) of the weighted loss of INTEGRATION.md -- w > 0 counts as w, anything else as 0, and a
+        pixel that does not count is replaced by the target before the SSIM windows are formed; its gradient is exactly 0. None: the unweighted loss."""
+        sums, grad, _ = self._l1_dssim(image, target, lambda_l1, lambda_dssim, with_grad, weight)
         return sums[2], grad, sums[:2]
 
-    def l1_dssim_forward(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2):
+    def l1_dssim_forward(self, image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2,
+                         weight: Optional[torch.Tensor] = None):
         """The loss value alone: returns (loss 0-dim tensor, (l1, ssim) tensor, scratch). `scratch` holds the derivative maps that
-        l1_dssim_backward turns into dloss/dimage -- the shape of an autograd loss node (forward saves, backward launches one kernel)."""
-        sums, _, scratch = self._l1_dssim(image, target, lambda_l1, lambda_dssim, False)
+        l1_dssim_backward turns into dloss/dimage -- the shape of an autograd loss node (forward saves, backward launches one kernel).
+        `weight` as in l1_dssim; hand the same one to l1_dssim_backward."""
+        sums, _, scratch = self._l1_dssim(image, target, lambda_l1, lambda_dssim, False, weight)
         return sums[2], sums[:2], scratch
 
     def l1_dssim_backward(self, image: torch.Tensor, target: torch.Tensor, scratch: torch.Tensor, upstream: Optional[torch.Tensor] = None,
-                          lambda_l1: float = 0.8, lambda_dssim: float = 0.2) -> torch.Tensor:
-        """dloss/dimage * upstream from the maps of l1_dssim_forward (same image / target). `upstream`: a float32 scalar tensor on the
-        device (dL/dloss), folded into the kernel -- no `grad * upstream` pass over the image -- or None for 1."""
+                          lambda_l1: float = 0.8, lambda_dssim: float = 0.2, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dloss/dimage * upstream from the maps of l1_dssim_forward (same image / target / weight). `upstream`: a float32 scalar tensor on the
+        device (dL/dloss), folded into the kernel -- no `grad * upstream` pass over the image -- or None for 1. The weight itself gets no gradient."""
         device = self._check_params((image, target), ('image', 'target'))
         _, h, w = image.shape
-        if scratch.device != device or scratch.numel() < int(self.lib.fgs_l1_dssim_scratch_bytes(w, h)):
+        if weight is not None:
+            weight = self._loss_weight(weight, image)
+        need = self.lib.fgs_l1_dssim_scratch_bytes(w, h) if weight is None else self.lib.fgs_l1_dssim_weighted_scratch_bytes(w, h)
+        if scratch.device != device or scratch.numel() < int(need):
             raise RuntimeError('l1_dssim_backward: scratch is not the buffer l1_dssim_forward returned for this image size')
         if upstream is not None:
             if upstream.device != device or upstream.dtype != torch.float32 or upstream.numel() != 1:
                 raise RuntimeError('l1_dssim_backward: upstream must be one float32 on the device of the image')
             upstream = upstream.reshape(1).contiguous()
         grad = torch.empty_like(image)
-        self._check(self.lib.fgs_l1_dssim_backward(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
-                                                   _ptr(upstream), grad.data_ptr(), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_backward')
+        if weight is None:
+            self._check(self.lib.fgs_l1_dssim_backward(image.data_ptr(), target.data_ptr(), w, h, float(lambda_l1), float(lambda_dssim),
+                                                       _ptr(upstream), grad.data_ptr(), scratch.data_ptr(), _stream_of(device)), 'fgs_l1_dssim_backward')
+        else:
+            self._check(self.lib.fgs_l1_dssim_weighted_backward(image.data_ptr(), target.data_ptr(), weight.data_ptr(), w, h, float(lambda_l1),
+                                                                float(lambda_dssim), _ptr(upstream), grad.data_ptr(), scratch.data_ptr(),
+                                                                _stream_of(device)), 'fgs_l1_dssim_weighted_backward')
         return grad
 
     # -- per-view bilateral-grid colour correction (include/fgs_hip.h, csrc/bilagrid.hip) ------------------------------------------

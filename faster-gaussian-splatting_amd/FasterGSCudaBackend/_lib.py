@@ -104,6 +104,9 @@ _SIGNATURES = {
     'fgs_l1_dssim_scratch_bytes': (C.c_size_t, [_I32, _I32]),
     'fgs_l1_dssim_loss': (C.c_int32, [_P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
     'fgs_l1_dssim_backward': (C.c_int32, [_P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
+    'fgs_l1_dssim_weighted_scratch_bytes': (C.c_size_t, [_I32, _I32]),
+    'fgs_l1_dssim_weighted_loss': (C.c_int32, [_P, _P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
+    'fgs_l1_dssim_weighted_backward': (C.c_int32, [_P, _P, _P, _I32, _I32, C.c_float, C.c_float, _P, _P, _P, _P]),
     'fgs_bilagrid_slice': (C.c_int32, [_P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P]),
     'fgs_bilagrid_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),
     'fgs_bilagrid_slice_backward': (C.c_int32, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -23,7 +23,21 @@ struct LossScratch {
     size_t plane3, partials_at;
     LossScratch(int width, int height) : plane3(3 * static_cast<size_t>(width) * static_cast<size_t>(height)), partials_at((3 * plane3 + 1) & ~static_cast<size_t>(1)) {}
     void point_maps(LossArgs& a, void* scratch) const { a.d_mu = static_cast<float*>(scratch); a.d_m11 = a.d_mu + plane3; a.d_m12 = a.d_m11 + plane3; }
+    // the weighted loss appends the tiles' weight sums and their total S to the same layout
+    void point_weighted(LossArgs& a, void* scratch, const float* weight, int width, int height) const {
+        point_maps(a, scratch);
+        a.weight = weight; a.partials = a.d_mu + partials_at; a.wpartials = a.partials + l1_dssim_partials(width, height);
+        a.total_weight = a.wpartials + l1_dssim_weight_partials(width, height);
+    }
 };
+
+const char* weighted_loss_refusal(const void* image, const void* target, const void* weight, const void* out, const void* scratch, int width, int height) {
+    if (!weight) return "weight is NULL (the unweighted loss is fgs_l1_dssim_loss / fgs_l1_dssim_backward)";
+    if (!image || !target || !out || !scratch) return "NULL image / target / output / scratch";
+    if (width <= 0 || height <= 0) return "non-positive image size";
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7u) != 0) return "scratch must be 8-byte aligned";
+    return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -268,6 +282,35 @@ int32_t fgs_l1_dssim_backward(const float* image, const float* target, int32_t w
     LossArgs a{};
     a.image = image; a.target = target; a.grad = grad_image; a.upstream = upstream;
     LossScratch(width, height).point_maps(a, const_cast<void*>(scratch));      // the maps a forward launch left there
+    a.width = width; a.height = height; a.lambda_l1 = lambda_l1; a.lambda_dssim = lambda_dssim;
+    { StageScope t(ST_LOSS, stream); FGS_HIP(launch_l1_dssim_backward(a, stream)); }
+    return FGS_OK;
+}
+
+size_t fgs_l1_dssim_weighted_scratch_bytes(int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return 0;
+    return sizeof(float) * (LossScratch(width, height).partials_at + l1_dssim_partials(width, height) + l1_dssim_weight_partials(width, height) + 1);
+}
+
+int32_t fgs_l1_dssim_weighted_loss(const float* image, const float* target, const float* weight, int32_t width, int32_t height, float lambda_l1,
+                                   float lambda_dssim, float* sums, float* grad_image, void* scratch, void* stream_) {
+    if (const char* why = weighted_loss_refusal(image, target, weight, sums, scratch, width, height)) return fail(FGS_ERR_INVALID_ARGUMENT, "fgs_l1_dssim_weighted_loss: %s", why);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    LossArgs a{};
+    a.image = image; a.target = target; a.sums = sums; a.grad = grad_image;
+    LossScratch(width, height).point_weighted(a, scratch, weight, width, height);
+    a.width = width; a.height = height; a.lambda_l1 = lambda_l1; a.lambda_dssim = lambda_dssim;
+    { StageScope t(ST_LOSS, stream); FGS_HIP(launch_l1_dssim(a, stream)); }
+    return FGS_OK;
+}
+
+int32_t fgs_l1_dssim_weighted_backward(const float* image, const float* target, const float* weight, int32_t width, int32_t height, float lambda_l1,
+                                       float lambda_dssim, const float* upstream, float* grad_image, const void* scratch, void* stream_) {
+    if (const char* why = weighted_loss_refusal(image, target, weight, grad_image, scratch, width, height)) return fail(FGS_ERR_INVALID_ARGUMENT, "fgs_l1_dssim_weighted_backward: %s", why);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    LossArgs a{};
+    a.image = image; a.target = target; a.grad = grad_image; a.upstream = upstream;
+    LossScratch(width, height).point_weighted(a, const_cast<void*>(scratch), weight, width, height);   // the maps and S a forward launch left there
     a.width = width; a.height = height; a.lambda_l1 = lambda_l1; a.lambda_dssim = lambda_dssim;
     { StageScope t(ST_LOSS, stream); FGS_HIP(launch_l1_dssim_backward(a, stream)); }
     return FGS_OK;

@@ -311,8 +311,13 @@ struct LossArgs {                       // fused L1 + DSSIM loss and its image g
     int width, height;
     float lambda_l1, lambda_dssim;
     const float* upstream;                       // device scalar dL/dloss the gradient is multiplied with, or nullptr (= 1)
+    // the weighted loss (INTEGRATION.md 'Weighted loss'); all three nullptr for the unweighted one
+    const float* weight;                         // [H,W] per-pixel weights shared by the channels: w > 0 counts as w, anything else (0, negative, NaN) as 0
+    float* wpartials;                            // scratch: the sum of the effective weights of every forward tile, one float per tile of ONE channel plane
+    float* total_weight;                         // scratch: S, their sum in a fixed order (written by the reduction, read by the backward kernel)
 };
 size_t l1_dssim_partials(int width, int height);   // number of floats in LossArgs::partials
+size_t l1_dssim_weight_partials(int width, int height);   // number of floats in LossArgs::wpartials
 hipError_t launch_l1_dssim(const LossArgs& a, hipStream_t s);
 hipError_t launch_l1_dssim_backward(const LossArgs& a, hipStream_t s);   // gradient only, from the maps a forward launch left in d_mu / d_m11 / d_m12
 

@@ -41,8 +41,9 @@ class BilateralGrids(torch.nn.Module):
         self.optimizer = torch.optim.Adam(list(self.grids), lr=lr, eps=1e-15)
 
     def corrected(self, loss_fn, view_index: int, tv_weight: float):
-        """loss_fn over the corrected image plus the weighted total variation of that view's grid: what training_iteration minimises with a module."""
-        return lambda image, target: loss_fn(self(image, view_index), target) + tv_weight * self.tv(view_index)
+        """loss_fn over the corrected image plus the weighted total variation of that view's grid: what training_iteration minimises with a module.
+        Keyword arguments (the per-pixel `weight` of photometric_loss) go through to loss_fn: the CORRECTED image is what gets weighted."""
+        return lambda image, target, **kw: loss_fn(self(image, view_index), target, **kw) + tv_weight * self.tv(view_index)
 
     # ---- checkpoints (harness/checkpoint.py): tensors and plain containers only ----
     @torch.no_grad()

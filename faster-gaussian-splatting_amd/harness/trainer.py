@@ -129,10 +129,11 @@ def l1_loss(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return (image - target).abs().mean()
 
 
-def photometric_loss(image: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """LAMBDA_L1 * L1 + LAMBDA_DSSIM * DSSIM with the garden weights 0.8 / 0.2 (fastergs_garden.yaml:98-99, Loss.py:15-16)."""
+def photometric_loss(image: torch.Tensor, target: torch.Tensor, weight: 'torch.Tensor | None' = None) -> torch.Tensor:
+    """LAMBDA_L1 * L1 + LAMBDA_DSSIM * DSSIM with the garden weights 0.8 / 0.2 (fastergs_garden.yaml:98-99, Loss.py:15-16).
+    weight: [H,W] mask or per-pixel confidence of the weighted loss (harness/loss.py); None is the unweighted one."""
     from .loss import l1_dssim_loss
-    return l1_dssim_loss(image, target, 0.8, 0.2)
+    return l1_dssim_loss(image, target, 0.8, 0.2) if weight is None else l1_dssim_loss(image, target, 0.8, 0.2, weight=weight)
 
 
 _UNIT = {}
@@ -151,7 +152,8 @@ def _unit_gradient(loss: torch.Tensor) -> torch.Tensor:
 def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration: int, *, densification_end: int = 14_900,
                        loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss, depth_target: 'torch.Tensor | None' = None,
                        depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False,
-                       bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0) -> torch.Tensor:
+                       bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0,
+                       loss_weight: 'torch.Tensor | None' = None) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
@@ -160,9 +162,14 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
     g.densification_info is then not updated. Gradients and loss are the same either way.
     bilagrid (harness.bilagrid.BilateralGrids, after its training_setup) with view_index: the rendered image passes through that view's bilateral grid
     before loss_fn, tv_weight * the grid's total variation is added to the loss, and the module's optimizer steps behind the Gaussians'. None (the
-    default): the step is exactly the one without."""
+    default): the step is exactly the one without.
+    loss_weight [H,W]: a mask or per-pixel confidence handed to loss_fn as `weight=` on every branch (photometric_loss: the weighted L1 + DSSIM of
+    harness/loss.py; with a bilagrid the corrected image is what gets weighted). None (the default): loss_fn is called as before."""
     if bilagrid is not None:
         loss_fn = bilagrid.corrected(loss_fn, view_index, tv_weight)
+    if loss_weight is not None:
+        unweighted_fn = loss_fn
+        loss_fn = lambda image, target: unweighted_fn(image, target, weight=loss_weight)
     g.update_learning_rate(iteration + 1)
     with_depth = depth_target is not None and depth_weight > 0.0
     if absgrad:

@@ -478,6 +478,19 @@ int32_t fgs_l1_dssim_loss(const float* image, const float* target, int32_t width
  * reference's loss node (fused_dssim: forward saves maps, backward launches one kernel). */
 int32_t fgs_l1_dssim_backward(const float* image, const float* target, int32_t width, int32_t height, float lambda_l1, float lambda_dssim,
                               const float* upstream, float* grad_image, const void* scratch, void* stream);
+/* The same loss with a per-pixel weight (masks, confidences; INTEGRATION.md "Weighted loss"). weight: fp32 [H,W], shared by the three channels;
+ * w^ = w where w > 0, else 0 (negative and NaN count as 0; infinite weights are the caller's error); S = sum w^. Pixels with w^ = 0 are REPLACED BY THE
+ * TARGET before the SSIM windows are formed (x'), so a mask boundary plants no edge:
+ *   out3[0] = sum w^ |x' - y| / (3 S),  out3[1] = sum w^ SSIM(x', y) / (3 S),  out3[2] = lambda_l1 * out3[0] + lambda_dssim * (1 - out3[1]);
+ * S = 0: (0, 1, 0) and a gradient of zeros. dloss/dimage is exactly 0.0f where w^ = 0, and nothing of `image` there is used (NaN included). The weight
+ * gets no gradient. All-ones weights give the bits of the unweighted functions. Same conventions as those: device `upstream` or NULL, no host
+ * synchronisation, no allocation; scratch of fgs_l1_dssim_weighted_scratch_bytes(width, height) bytes, 8-byte aligned, shared by the two calls. A NULL
+ * weight, a NULL required pointer, a non-positive size or a misaligned scratch is refused with FGS_ERR_INVALID_ARGUMENT. */
+size_t fgs_l1_dssim_weighted_scratch_bytes(int32_t width, int32_t height);
+int32_t fgs_l1_dssim_weighted_loss(const float* image, const float* target, const float* weight, int32_t width, int32_t height, float lambda_l1,
+                                   float lambda_dssim, float* out3, float* grad_image, void* scratch, void* stream);
+int32_t fgs_l1_dssim_weighted_backward(const float* image, const float* target, const float* weight, int32_t width, int32_t height, float lambda_l1,
+                                       float lambda_dssim, const float* upstream, float* grad_image, const void* scratch, void* stream);
 
 /* ---- Per-view bilateral-grid colour correction between the rasterizer and the loss (csrc/bilagrid.hip; INTEGRATION.md "Bilateral grids") ----
  * grid: fp32 [12, grid_l, grid_h, grid_w], contiguous, every extent >= 1; channel 4 i + j is entry (i, j) of a 3 x 4 matrix [A | b]. For pixel (px, py)
