@@ -440,14 +440,74 @@ class Backend:
             int(bool(detach_geometry)), _stream_of(device)), 'fgs_backward_features')
         return grads + (grad_features,)
 
+    @staticmethod
+    def _check_distortion_means(means: torch.Tensor, n: int, device: torch.device) -> None:
+        if means.dim() != 2 or tuple(means.shape) != (n, 3) or means.dtype != torch.float32 or not means.is_contiguous() or means.device != device:
+            raise RuntimeError(f'means must be a contiguous float32 [N, 3] = [{n}, 3] tensor on the device of the forward pass, not '
+                               f'{tuple(means.shape)} {means.dtype} on {means.device}')
+
+    def blend_distortion(self, means: torch.Tensor, result, n_primitives: int, settings: RasterizerSettings, normalized: bool = True) -> torch.Tensor:
+        """fgs_blend_distortion: the depth-distortion state [3,H,W] of the pairs the training blend of `result` (a synchronous forward / forward_aux
+        over `n_primitives` Gaussians with these means and settings) blended. Plane 0 is the map X = sum_ab w_a w_b |t_a - t_b|, t = the view-space
+        depth (normalized=False) or its mapping onto [0, 1) with the settings' near and far planes; planes 1 and 2 are `backward_distortion`'s."""
+        device = result.image.device
+        n = int(n_primitives)
+        self._check_distortion_means(means, n, device)
+        keep: list = []
+        S = self._settings(settings, int(settings.active_sh_bases) - 1, device, keep)      # the blend reads no SH coefficient: any consistent count
+        st = _lib.ForwardState(*result.state)
+        dstate = torch.empty((3, int(settings.height), int(settings.width)), dtype=torch.float32, device=device)
+        b = result.buffers
+        self._check(self.lib.fgs_blend_distortion(_ptr(means), _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), n, C.byref(S), C.byref(st),
+                                                  _lib.DISTORTION_NORMALIZED if normalized else _lib.DISTORTION_LINEAR, dstate.data_ptr(),
+                                                  _stream_of(device)), 'fgs_blend_distortion')
+        return dstate
+
+    def backward_distortion(self, densification_info, grad_image, grad_distortion, image, distortion_state, means, scales, rotations, opacities,
+                            sh_rest, buffers, settings, state, normalized: bool = True, live_blocks: Optional[torch.Tensor] = None,
+                            reached_blocks: Optional[torch.Tensor] = None) -> tuple:
+        """fgs_backward_distortion: the six gradients of `backward` for a loss that also depends on plane 0 of `blend_distortion`'s state (same
+        `normalized`). grad_distortion [H,W] or None: None is `backward` exactly. Gradients come back in fresh tensors."""
+        if grad_distortion is None:
+            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state,
+                                 live_blocks=live_blocks, reached_blocks=reached_blocks)
+        device = self._check_params((means, scales, rotations, opacities, sh_rest), BACKWARD_PARAMETER_NAMES)
+        n = means.shape[0]
+        hw = (int(settings.height), int(settings.width))
+        if tuple(grad_distortion.shape) != hw or grad_distortion.device != device:
+            raise RuntimeError(f'grad_distortion must be a [H,W] = {hw} tensor on the parameters\' device')
+        if tuple(distortion_state.shape) != (3,) + hw or distortion_state.device != device:
+            raise RuntimeError(f'distortion_state must be the [3,H,W] = {(3,) + hw} tensor blend_distortion returned')
+        distortion_state = distortion_state.to(dtype=torch.float32).contiguous()
+        grad_distortion = grad_distortion.to(dtype=torch.float32).contiguous()
+        grad_image = grad_image.to(dtype=torch.float32).contiguous()
+        keep: list = []
+        total_rest = total_sh_rest(sh_rest)
+        S = self._settings(settings, total_rest, device, keep)
+        grads = _gradients_out(None, gradient_shapes(n, total_rest), device)
+        dens = _densification(densification_info, n, device, validate=True)
+        _check_block_flags('live_blocks', live_blocks, n, device)
+        _check_block_flags('reached_blocks', reached_blocks, n, device)
+        scratch = self._scratch_aux(n, settings, device)                # dL/dz of the distortion term lives in the aux layout's acc_z
+        st = _lib.ForwardState(*state)
+        self._check(self.lib.fgs_backward_distortion(
+            _ptr(grad_image), _ptr(image), None, None, None, _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh_rest),
+            _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
+            _ptr(grads[4]), _ptr(grads[5]), _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+            _ptr(distortion_state), grad_distortion.data_ptr(), _lib.DISTORTION_NORMALIZED if normalized else _lib.DISTORTION_LINEAR,
+            _stream_of(device)), 'fgs_backward_distortion')
+        return grads
+
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
                             buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,
-                            grad_alpha=None, grad_depth=None, grad_feature_map=None) -> None:
+                            grad_alpha=None, grad_depth=None, grad_feature_map=None, grad_distortion=None) -> None:
         """params / moments / lrs in optimizer-group order: means, sh0, sh_rest, opacities, scales, rotations (Model.py:238-245)."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_adam_fused takes no alpha / depth gradients: use backward_aux and an optimizer step of its own')
         if grad_feature_map is not None:
             raise RuntimeError('backward_adam_fused takes no feature-map gradient: use backward_features and an optimizer step of its own')
+        if grad_distortion is not None:
+            raise RuntimeError('backward_adam_fused takes no distortion gradient: use backward_distortion and an optimizer step of its own')
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         keep: list = []
         n = params[0].shape[0]
@@ -685,12 +745,14 @@ class Backend:
 
     def backward_to_records(self, grad_image, image, buffers, settings: RasterizerSettings, state, total_sh_rest: int,
                             out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None,
-                            grad_feature_map=None) -> torch.Tensor:
+                            grad_feature_map=None, grad_distortion=None) -> torch.Tensor:
         """K11 of a view rendered by `forward_from_records` -> float32 [n_records, 9] accumulator records."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_to_records takes no alpha / depth gradients: the sharded and record paths render colour only')
         if grad_feature_map is not None:
             raise RuntimeError('backward_to_records takes no feature-map gradient: the sharded and record paths render colour only')
+        if grad_distortion is not None:
+            raise RuntimeError('backward_to_records takes no distortion gradient: the sharded and record paths render colour only')
         device = image.device
         n = int(state[0])
         keep: list = []

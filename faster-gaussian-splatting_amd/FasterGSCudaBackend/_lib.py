@@ -42,6 +42,7 @@ class BlobEntry(C.Structure):
 
 
 SPLAT_RECORD_BYTES, ACC_RECORD_BYTES = 56, 36        # FGS_SPLAT_RECORD_BYTES / FGS_ACC_RECORD_BYTES
+DISTORTION_LINEAR, DISTORTION_NORMALIZED = 0, 1      # FGS_DISTORTION_*
 
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
 
@@ -64,6 +65,9 @@ _SIGNATURES = {
     'fgs_blend_features': (C.c_int32, [_P, _I32, _P, _P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P]),
     'fgs_backward_features': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P,
                                           _P, _I32, _P, _P, _P, _I32, _P]),
+    'fgs_blend_distortion': (C.c_int32, [_P, _P, _P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _I32, _P, _P]),
+    'fgs_backward_distortion': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P,
+                                            _P, _P, _I32, _P]),
     'fgs_forward_async': (C.c_int32, [_P] * 6 + [_I32, C.POINTER(Settings), _P, _I32, RESIZE_FN, _P, C.POINTER(ForwardState), _P]),
     'fgs_forward_counts': (C.c_int32, [_P, _I32, _P, _P]),
     'fgs_backward_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),

@@ -648,6 +648,53 @@ def diff_rasterize_features(means: torch.Tensor, scales: torch.Tensor, rotations
                                     rasterizer_settings, bool(detach_geometry))
 
 
+class _RasterizeDistortion(torch.autograd.Function):
+    """_Rasterize that also returns the depth-distortion map of the same pass, differentiable through the compositing weights and the depths of the
+    Gaussians (fgs_blend_distortion / fgs_backward_distortion). Always the synchronous forward pass; gradients in fresh tensors (no arena, no
+    live-block hand-over)."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                rasterizer_settings: RasterizerSettings, normalized: bool):
+        _require_gpu(means)
+        be = default_backend()
+        res = be.forward(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, rasterizer_settings)
+        state = be.blend_distortion(means, res, means.shape[0], rasterizer_settings, normalized)
+        ctx.rasterizer_settings = rasterizer_settings
+        ctx.buffer_state = res.state
+        ctx.normalized = bool(normalized)
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None (= zero), not as a tensor of zeros
+        ctx.save_for_backward(res.image, state, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.mark_non_differentiable(densification_info)
+        return res.image, state[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_distortion):
+        image, state, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        clear_live_blocks([means])
+        # a distortion map that is not part of the loss costs nothing: the pass is then the plain one
+        grads = default_backend().backward_distortion(
+            ctx.densification_info, grad_image.contiguous(), grad_distortion.contiguous() if grad_distortion is not None else None, image, state,
+            means, scales, rotations, opacities, sh_rest, buffers, ctx.rasterizer_settings, ctx.buffer_state, ctx.normalized)
+        return (*grads, None, None, None)
+
+
+def diff_rasterize_distortion(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                              sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                              rasterizer_settings: RasterizerSettings, normalized: bool = True):
+    """Training render that also returns, differentiable, the depth-distortion map of Mip-NeRF 360 / 2DGS: (image [3,H,W], distortion [H,W]) with
+    distortion[p] = sum_a sum_b w_a w_b |t_a - t_b| over the pairs the image blended in pixel p (w_i = T_i alpha_i). t is the view-space depth z of the
+    Gaussian's mean, mapped onto [0, 1) as far (z - near) / ((far - near) z) with the settings' planes unless normalized=False. A regulariser
+    `weight * distortion.mean()` pulls the weight of each ray onto one surface. One extra walk forward and one backward; a map the loss does not use
+    costs nothing in the backward pass. The image is diff_rasterize's. No gradient for the planes."""
+    return _RasterizeDistortion.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info,
+                                      rasterizer_settings, bool(normalized))
+
+
 def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
               sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
               to_chw: bool, clamp_output: bool = True) -> torch.Tensor:

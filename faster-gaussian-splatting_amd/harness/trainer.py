@@ -13,7 +13,7 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_features, rasterize,
+from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_distortion, diff_rasterize_features, rasterize,
                                  rasterize_aux)
 
 from .scenes import View
@@ -103,6 +103,13 @@ def render_image_training_features(g: Gaussians, view: View, update_densificatio
                                    detach_geometry=detach_geometry)
 
 
+def render_image_training_distortion(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, normalized: bool = True):
+    """render_image_training plus the differentiable depth-distortion map X = sum_ab w_a w_b |t_a - t_b| per pixel: (image, distortion [H,W])."""
+    return diff_rasterize_distortion(*g.tensors(),
+                                     densification_info=g.densification_info if update_densification_info else torch.empty(0),
+                                     rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), normalized=normalized)
+
+
 def depth_l1_loss(alpha: torch.Tensor, depth: torch.Tensor, depth_target: torch.Tensor, valid: 'torch.Tensor | None' = None) -> torch.Tensor:
     """L1 between the mean depth D / A.clamp_min(1e-8) and the target over the valid pixels (default: target > 0)."""
     valid = depth_target > 0 if valid is None else valid
@@ -153,7 +160,8 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
                        loss_scale: float = 1.0, before_step=None, loss_fn=photometric_loss, depth_target: 'torch.Tensor | None' = None,
                        depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False,
                        bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0,
-                       loss_weight: 'torch.Tensor | None' = None) -> torch.Tensor:
+                       loss_weight: 'torch.Tensor | None' = None, distortion_weight: float = 0.0,
+                       distortion_normalized: bool = True) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
@@ -164,7 +172,12 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
     before loss_fn, tv_weight * the grid's total variation is added to the loss, and the module's optimizer steps behind the Gaussians'. None (the
     default): the step is exactly the one without.
     loss_weight [H,W]: a mask or per-pixel confidence handed to loss_fn as `weight=` on every branch (photometric_loss: the weighted L1 + DSSIM of
-    harness/loss.py; with a bilagrid the corrected image is what gets weighted). None (the default): loss_fn is called as before."""
+    harness/loss.py; with a bilagrid the corrected image is what gets weighted). None (the default): loss_fn is called as before.
+    distortion_weight > 0 adds distortion_weight * distortion.mean(), the depth-distortion regulariser of diff_rasterize_distortion (t normalized onto
+    [0, 1) with the view's planes unless distortion_normalized=False). Not together with depth supervision or absgrad. 0 (the default): the step is
+    exactly the one without."""
+    if distortion_weight > 0.0 and (absgrad or (depth_target is not None and depth_weight > 0.0)):
+        raise ValueError('training_iteration: the distortion term does not combine with depth supervision or absgrad in one render')
     if bilagrid is not None:
         loss_fn = bilagrid.corrected(loss_fn, view_index, tv_weight)
     if loss_weight is not None:
@@ -179,6 +192,10 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
     elif with_depth:
         image, alpha, depth = render_image_training_aux(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
         loss = loss_fn(image, target) + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid)
+    elif distortion_weight > 0.0:
+        image, distortion = render_image_training_distortion(g, view, update_densification_info=iteration < densification_end,
+                                                             bg_color=view.background_color, normalized=distortion_normalized)
+        loss = loss_fn(image, target) + distortion_weight * distortion.mean()
     else:
         image = render_image_training(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
         loss = loss_fn(image, target)

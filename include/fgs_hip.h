@@ -246,6 +246,43 @@ int32_t fgs_backward_features(const float* grad_image, const float* image, const
                               uint8_t* reached_blocks, const float* features, int32_t n_channels, const float* feature_map,
                               const float* grad_feature_map, float* grad_features, int32_t detach_geometry, void* stream);
 
+/* Depth-distortion regulariser of the training pass (Mip-NeRF 360's distortion loss; the `distloss` of 2DGS). Over exactly the (pixel, Gaussian) pairs
+ * the training blend of the forward pass blended, in its order i = 1..n -- the same sub-tile cull, alpha >= 1/255, T_before >= 1e-4, never beyond the
+ * pixel's last contributor -- with w_i = T_before_i alpha_i and a depth value t_i per Gaussian:
+ *     X(p) = sum_a sum_b w_a w_b |t_a - t_b| = 2 sum_i w_i (t_i A_{i-1} - D_{i-1}),    A_i = sum_{j<=i} w_j,  D_i = sum_{j<=i} w_j t_j
+ * (the lists are in depth order, so t does not decrease along the walk). mode FGS_DISTORTION_LINEAR: t_i = z_i, row 2 of w2c applied to the mean, as in
+ * fgs_forward_aux. FGS_DISTORTION_NORMALIZED: t_i = far (z_i - near) / ((far - near) z_i), onto [0, 1) with the settings' near_plane and far_plane.
+ * distortion_state: fp32 [3, H, W], every element written. Plane 0 is X, exactly 0 where fewer than two Gaussians were blended; planes 1 and 2 are what
+ * fgs_backward_distortion needs and are the library's private format (the walk shifts t by a tile-uniform origin, under which X does not change).
+ * `means` are the Gaussians' of the forward pass; the buffers and `state` are those of a completed SYNCHRONOUS fgs_forward or fgs_forward_aux over them
+ * with the same settings; they are read only, and stay valid input to every backward pass.
+ * FGS_ERR_INVALID_ARGUMENT, never ignored: a mode other than the two, near_plane <= 0 or far_plane <= near_plane in normalized mode, NULL
+ * distortion_state, NULL means (n_primitives > 0), buffers of fgs_forward_async or of the record / sharded forward passes. n_primitives == 0: a zero
+ * state, nothing else is written. */
+enum { FGS_DISTORTION_LINEAR = 0, FGS_DISTORTION_NORMALIZED = 1 };
+int32_t fgs_blend_distortion(const float* means, const void* primitive_buffers, const void* tile_buffers, const void* instance_buffers,
+                             int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, int32_t mode, float* distortion_state,
+                             void* stream);
+/* fgs_backward_reached for a loss that also depends on X: distortion_state = what fgs_blend_distortion wrote (same mode), grad_distortion = the
+ * upstream gradient of plane 0, [H, W]. With e_i = dX/dw_i = 2 [t_i (2 A_{i-1} - A_n) - 2 D_{i-1} + D_n] and S_i = sum_{j>i} w_j e_j = 2 X - sum_{j<=i} w_j e_j
+ * (the forward state takes the place of per-bucket checkpoints):
+ *     dL/dalpha_i(p) += gX [T_i e_i - S_i / max(1 - alpha_i, 1e-6)]              added to the colour term's per-Gaussian sums, then K12 as always
+ *     dL/dz_i         = sum_p gX 2 w_i (2 A_{i-1} + w_i - A_n) dt_i/dz_i          grad_means[i] += dL/dz_i w2c[2, 0:3] behind K12
+ * The kernels run K11, the distortion backward blend, K12, the depth term of the means. dL/dz takes part in K12's "did the blend pass reach it" test,
+ * so live_blocks / reached_blocks mean what they mean in fgs_backward_reached. scratch: fgs_backward_aux_scratch_bytes (the plain layout is its prefix),
+ * with or without map gradients. grad_distortion == NULL IS fgs_backward_reached: the distortion arguments are not looked at and the scratch is that
+ * pass's. Refused like fgs_blend_distortion, and a NULL distortion_state; the fused backward + Adam, asynchronous, sharded and record paths and the
+ * pose, feature and absgrad entry points take no distortion gradient. No gradient for near_plane / far_plane. n_primitives == 0 writes nothing. */
+int32_t fgs_backward_distortion(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                                const float* means, const float* scales, const float* rotations, const float* opacities,
+                                const float* sh_coefficients_rest,
+                                void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                                float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                                float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                                float* densification_info, void* scratch,
+                                int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                                uint8_t* reached_blocks, const float* distortion_state, const float* grad_distortion, int32_t mode, void* stream);
+
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
  * the largest count fgs_forward_counts() has reported, scaled with the primitive count -- and every kernel reads the exact counts on the
