@@ -9,6 +9,7 @@ A check that several entries make is one function below; where the entries diffe
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Optional, Sequence
 
 import torch
@@ -855,9 +856,14 @@ class Backend:
         total_rest = total_sh_rest(params[2])
         scratch = _empty_bytes(self.lib.fgs_adc_scratch_bytes(n), device)
         counts = (C.c_int32 * 4)()
-        self._check(self.lib.fgs_adc_plan(_ptr(densification_info), _ptr(params[4]), _ptr(params[5]), _ptr(params[3]), n, float(grad_threshold),
-                                          float(min_opacity), int(bool(prune_large_gaussians)), float(percent_dense), float(extent),
-                                          scratch.data_ptr(), counts, _stream_of(device)), 'fgs_adc_plan')
+        # the reference's thresholds (Model.py:315, 360, 363): formed in double from the Python scalars and rounded to float32 once, at the comparison
+        if not (0.0 < min_opacity < 1.0) or not (percent_dense * extent > 0.0):
+            raise RuntimeError('adaptive_density_control: min_opacity / percent_dense * extent out of range')
+        log_small, log_large = math.log(percent_dense * extent), math.log(0.1 * extent)
+        min_opacity_logit = math.log(min_opacity / (1 - min_opacity))
+        self._check(self.lib.fgs_adc_plan_thresholds(_ptr(densification_info), _ptr(params[4]), _ptr(params[5]), _ptr(params[3]), n, float(grad_threshold),
+                                                     min_opacity_logit, int(bool(prune_large_gaussians)), log_small, log_large,
+                                                     scratch.data_ptr(), counts, _stream_of(device)), 'fgs_adc_plan_thresholds')
         kept, clones, children, split = (int(c) for c in counts)
         n_new = kept + clones + 2 * children
         noise = (noise_fn(2 * split) if noise_fn is not None else torch.randn((2 * split, 3), device=device)).to(device=device, dtype=torch.float32).contiguous()
@@ -869,6 +875,8 @@ class Backend:
         out_m = [make(t) for t in params] if have_state else None
         out_v = [make(t) for t in params] if have_state else None
         arr = lambda ts: _pointer_array(ts, 6) if ts is not None else None
+        if n_new == 0:                     # everything pruned: nothing to write, and empty tensors have no address to hand over
+            return out_p, out_m, out_v, (kept, clones, children, split)
         self._check(self.lib.fgs_adc_apply(arr(params), arr(exp_avgs), arr(exp_avg_sqs), arr(out_p), arr(out_m), arr(out_v), _ptr(noise),
                                            scratch.data_ptr(), n, total_rest, _stream_of(device)), 'fgs_adc_apply')
         return out_p, out_m, out_v, (kept, clones, children, split)

@@ -172,12 +172,12 @@ size_t fgs_adc_scratch_bytes(int32_t n_primitives) {
     return c.total();
 }
 
-int32_t fgs_adc_plan(const float* densification_info, const float* scales, const float* rotations, const float* opacities, int32_t n_primitives,
-                     float grad_threshold, float min_opacity, int32_t prune_large_gaussians, float percent_dense, float extent,
-                     void* scratch, int32_t* counts_out, void* stream_) {
+int32_t fgs_adc_plan_thresholds(const float* densification_info, const float* scales, const float* rotations, const float* opacities, int32_t n_primitives,
+                                float grad_threshold, float min_opacity_logit, int32_t prune_large_gaussians, float log_small, float log_large,
+                                void* scratch, int32_t* counts_out, void* stream_) {
     if (n_primitives < 0 || !counts_out || !scratch) return fail(FGS_ERR_INVALID_ARGUMENT, "bad argument");
     if (n_primitives > 0 && (!densification_info || !scales || !rotations || !opacities)) return fail(FGS_ERR_INVALID_ARGUMENT, "NULL tensor");
-    if (!(min_opacity > 0.0f && min_opacity < 1.0f) || !(percent_dense * extent > 0.0f)) return fail(FGS_ERR_INVALID_ARGUMENT, "min_opacity / percent_dense * extent out of range");
+    if (min_opacity_logit != min_opacity_logit || log_small != log_small || log_large != log_large) return fail(FGS_ERR_INVALID_ARGUMENT, "a threshold is NaN");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Carver c(scratch);
     const AdcScratch sc = AdcScratch::carve(c, static_cast<uint32_t>(n_primitives));
@@ -185,9 +185,7 @@ int32_t fgs_adc_plan(const float* densification_info, const float* scales, const
     a.densification_info = densification_info; a.scales = scales; a.rotations = rotations; a.opacities = opacities;
     a.n = static_cast<uint32_t>(n_primitives);
     a.grad_threshold = grad_threshold;
-    a.min_opacity_logit = static_cast<float>(std::log(static_cast<double>(min_opacity) / (1.0 - static_cast<double>(min_opacity))));   // Model.py:360
-    a.log_small = static_cast<float>(std::log(static_cast<double>(percent_dense) * static_cast<double>(extent)));                         // :315
-    a.log_large = static_cast<float>(std::log(0.1 * static_cast<double>(extent)));                                                         // :363
+    a.min_opacity_logit = min_opacity_logit; a.log_small = log_small; a.log_large = log_large;
     a.prune_large = prune_large_gaussians ? 1 : 0;
     a.plan = sc.plan; a.offsets = sc.offsets; a.totals = sc.totals; a.scan_temp = sc.scan_temp; a.scan_temp_bytes = sc.scan_temp_bytes;
     FGS_HIP(launch_adc_plan(a, stream));
@@ -196,6 +194,19 @@ int32_t fgs_adc_plan(const float* densification_info, const float* scales, const
     FGS_HIP(hipStreamSynchronize(stream));
     for (int k = 0; k < 4; ++k) counts_out[k] = static_cast<int32_t>(host[k]);
     return FGS_OK;
+}
+
+// The thresholds from float arguments: what a caller that holds float32 values gets. The reference forms them from Python doubles (0.01 is not
+// float(0.01f)), which a float argument cannot carry: FasterGSCudaBackend goes through fgs_adc_plan_thresholds.
+int32_t fgs_adc_plan(const float* densification_info, const float* scales, const float* rotations, const float* opacities, int32_t n_primitives,
+                     float grad_threshold, float min_opacity, int32_t prune_large_gaussians, float percent_dense, float extent,
+                     void* scratch, int32_t* counts_out, void* stream) {
+    if (!(min_opacity > 0.0f && min_opacity < 1.0f) || !(percent_dense * extent > 0.0f)) return fail(FGS_ERR_INVALID_ARGUMENT, "min_opacity / percent_dense * extent out of range");
+    const float min_opacity_logit = static_cast<float>(std::log(static_cast<double>(min_opacity) / (1.0 - static_cast<double>(min_opacity))));   // Model.py:360
+    const float log_small = static_cast<float>(std::log(static_cast<double>(percent_dense) * static_cast<double>(extent)));                         // :315
+    const float log_large = static_cast<float>(std::log(0.1 * static_cast<double>(extent)));                                                         // :363
+    return fgs_adc_plan_thresholds(densification_info, scales, rotations, opacities, n_primitives, grad_threshold, min_opacity_logit, prune_large_gaussians,
+                                   log_small, log_large, scratch, counts_out, stream);
 }
 
 int32_t fgs_adc_apply(const float* const* params, const float* const* exp_avgs, const float* const* exp_avg_sqs,

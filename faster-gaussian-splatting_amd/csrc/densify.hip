@@ -12,12 +12,20 @@
 // Output order of adaptive density control (identical to the reference's cat / boolean-index result): the surviving old Gaussians in
 // their order, then the surviving clones in the order of their originals, then the surviving first children of the split Gaussians,
 // then the surviving second children. New Gaussians start with zero Adam moments (extend_param_groups), survivors keep theirs.
-// Built with -ffp-contract=off (Makefile): keys and thresholds reproduce the numpy restatement of Model.py that the tests compare with, bit for bit.
+// Built with -ffp-contract=off (Makefile): keys and thresholds reproduce the numpy restatement of Model.py that the tests compare with, bit for bit
+// (the three thresholds arrive as the float32 values the reference compares with, fgs_adc_plan_thresholds; INTEGRATION.md "Density control: thresholds").
 #include "fgs_kernels.h"
 #include <fgs_wave.h>
 #include "fgs_tile_scan.h"
 
 namespace fgs {
+
+// the largest of three as torch.max(dim=1) and numpy's max form it: a NaN component is the result (fmaxf would drop it). Every comparison with
+// a NaN is false, so such a Gaussian is neither small (it is split when it densifies) nor too large.
+__device__ __forceinline__ float max3_nan(const float a, const float b, const float c) {
+    const float m = fmaxf(a, fmaxf(b, c));
+    return (a != a || b != b || c != c) ? __builtin_nanf("") : m;
+}
 
 // per-Gaussian plan word: bit 0 keep the old one, bit 1 keep its clone, bit 2 keep its two children, bit 3 it is split at all
 __global__ void __launch_bounds__(256) adc_classify_kernel(const AdcPlanArgs a) {
@@ -26,14 +34,14 @@ __global__ void __launch_bounds__(256) adc_classify_kernel(const AdcPlanArgs a) 
     const float count = a.densification_info[i], grad_sum = a.densification_info[(size_t)a.n + i];
     const bool densify = grad_sum >= a.grad_threshold * fmaxf(count, 1.0f);                                   // Model.py:314
     const float s0 = a.scales[3 * (size_t)i], s1 = a.scales[3 * (size_t)i + 1], s2 = a.scales[3 * (size_t)i + 2];
-    const float s_max = fmaxf(s0, fmaxf(s1, s2));
+    const float s_max = max3_nan(s0, s1, s2);
     const bool is_small = s_max <= a.log_small;                                                                // :315
     const bool duplicate = densify && is_small, split = densify && !is_small;                                  // :318, :328
     const float q0 = a.rotations[4 * (size_t)i], q1 = a.rotations[4 * (size_t)i + 1], q2 = a.rotations[4 * (size_t)i + 2], q3 = a.rotations[4 * (size_t)i + 3];
     const bool dead = a.opacities[i] < a.min_opacity_logit || (q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3) < 1e-8f;  // :360-361
     const bool too_large = a.prune_large && s_max > a.log_large;                                               // :362-363
     // the children's scales are log(0.625 exp(s)) (:333): the same expression the scatter pass stores, so the test sees the stored value
-    const float child_max = fmaxf(logf(expf(s0) * 0.625f), fmaxf(logf(expf(s1) * 0.625f), logf(expf(s2) * 0.625f)));
+    const float child_max = max3_nan(logf(expf(s0) * 0.625f), logf(expf(s1) * 0.625f), logf(expf(s2) * 0.625f));
     const bool child_too_large = a.prune_large && child_max > a.log_large;
     uint32_t word = 0;
     if (!split && !dead && !too_large) word |= 1u;                // :359: a split Gaussian is replaced by its children

@@ -482,11 +482,21 @@ int32_t fgs_add_noise(const float* raw_scales, const float* raw_rotations, const
  *                  in their order with their moments, then clones, then first children, then second children, all with zero moments.
  *                  Children: means + R(q) (exp(s) * noise) with noise [2 * counts[3], 3] ~ N(0,1) from the caller (row = copy * counts[3]
  *                  + rank among the split Gaussians, the layout of the reference's randn_like), scales log(0.625 exp(s)).
- * scratch: fgs_adc_scratch_bytes(n) bytes, the same buffer for both calls. */
+ *                  When the new size is 0 there is nothing to apply and no tensor to pass: do not call it (NULL tensors are refused).
+ * scratch: fgs_adc_scratch_bytes(n) bytes, the same buffer for both calls.
+ * Thresholds. The reference compares float32 tensors with Python doubles, which torch rounds to float32 ONCE: log(percent_dense * extent),
+ * log(0.1 * extent) and log(min_opacity / (1 - min_opacity)) evaluated in double. fgs_adc_plan_thresholds takes those three values as the caller
+ * rounded them (log_small, log_large, min_opacity_logit; NaN is refused) and is what reproduces the reference bit for bit; fgs_adc_plan forms them
+ * from its float arguments, i.e. from float(percent_dense) and float(extent), which is one ulp away for about one extent in seven (log_small)
+ * and one in two (log_large). Non-finite inputs are not sanitised: the comparisons are the reference's, a NaN scale component makes the largest scale NaN
+ * (not small, not too large), a NaN opacity or rotation is not dead, a NaN gradient sum does not densify. */
 size_t fgs_adc_scratch_bytes(int32_t n_primitives);
 int32_t fgs_adc_plan(const float* densification_info, const float* scales, const float* rotations, const float* opacities, int32_t n_primitives,
                      float grad_threshold, float min_opacity, int32_t prune_large_gaussians, float percent_dense, float extent,
                      void* scratch, int32_t* counts_out, void* stream);
+int32_t fgs_adc_plan_thresholds(const float* densification_info, const float* scales, const float* rotations, const float* opacities, int32_t n_primitives,
+                                float grad_threshold, float min_opacity_logit, int32_t prune_large_gaussians, float log_small, float log_large,
+                                void* scratch, int32_t* counts_out, void* stream);
 int32_t fgs_adc_apply(const float* const* params, const float* const* exp_avgs, const float* const* exp_avg_sqs,
                       float* const* out_params, float* const* out_exp_avgs, float* const* out_exp_avg_sqs,
                       const float* noise, const void* scratch, int32_t n_primitives, int32_t total_sh_bases_rest, void* stream);

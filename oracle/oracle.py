@@ -476,6 +476,22 @@ def add_noise(raw_scales, raw_rotations, raw_opacities, random_samples, means, c
 
 
 # ---- maintenance of the Gaussian set, restated in numpy fp32 -------------------------------------------------
+def adc_masks(densification_info, opacities, scales, rotations, grad_threshold: float, min_opacity: float, percent_dense: float, extent: float) -> dict:
+    """The four row masks of Model.py:312-366 as adaptive_density_control below applies them (tests/test_adc_edges.py holds them to the same
+    expressions in torch): every threshold is formed in double from the Python scalars and rounded to float32 once, where torch compares a float32
+    tensor with it; the row-wise max returns a NaN component. densification_info None: no 'densify' entry (the rows added by the densification)."""
+    f = np.float32
+    scales, rotations = _f32(scales), _f32(rotations)
+    s_max = scales.max(axis=1)
+    masks = {'small': s_max <= f(np.log(percent_dense * extent)),                                                             # :315
+             'dead': (_f32(opacities).reshape(-1) < f(np.log(min_opacity / (1 - min_opacity)))) | ((rotations * rotations).sum(axis=1) < f(1e-8)),   # :360-361
+             'too_large': s_max > f(np.log(0.1 * extent))}                                                                   # :363
+    if densification_info is not None:
+        info = _f32(densification_info)
+        masks['densify'] = info[1] >= f(grad_threshold) * np.maximum(info[0], f(1.0))                                         # :314
+    return masks
+
+
 def adaptive_density_control(params: dict, exp_avgs: dict | None, exp_avg_sqs: dict | None, densification_info: np.ndarray, noise: np.ndarray,
                              grad_threshold: float, min_opacity: float, prune_large_gaussians: bool, percent_dense: float, extent: float):
     """Model.py:312-366 line by line (with extend_param_groups / prune_param_groups of the un-vendored NeRFICG Optim.adam_utils: new
@@ -487,8 +503,8 @@ def adaptive_density_control(params: dict, exp_avgs: dict | None, exp_avg_sqs: d
     P = {k: _f32(params[k]) for k in keys}
     info = _f32(densification_info)
     scales, rotations = P['scales'], P['rotations']
-    densification_mask = info[1] >= f(grad_threshold) * np.maximum(info[0], f(1.0))                                         # :314
-    is_small = scales.max(axis=1) <= f(np.log(percent_dense * extent))                                                        # :315
+    old = adc_masks(info, P['opacities'], scales, rotations, grad_threshold, min_opacity, percent_dense, extent)
+    densification_mask, is_small = old['densify'], old['small']                                                               # :314-315
     duplicate_mask = densification_mask & is_small                                                                            # :318
     split_mask = densification_mask & ~is_small                                                                               # :328
     n_split = int(split_mask.sum())
@@ -512,10 +528,10 @@ def adaptive_density_control(params: dict, exp_avgs: dict | None, exp_avg_sqs: d
     n_new = extra['means'].shape[0]
     full = {k: np.concatenate([P[k], extra[k]]) for k in keys}                                                                # :340-347 extend_param_groups
     prune_mask = np.concatenate([split_mask, np.zeros(n_new, bool)])                                                          # :359
-    prune_mask |= full['opacities'].reshape(-1) < f(np.log(min_opacity / (1 - min_opacity)))                                  # :360
-    prune_mask |= (full['rotations'] * full['rotations']).sum(axis=1) < f(1e-8)                                               # :361
+    new = adc_masks(None, full['opacities'], full['scales'], full['rotations'], grad_threshold, min_opacity, percent_dense, extent)
+    prune_mask |= new['dead']                                                                                                 # :360-361
     if prune_large_gaussians:
-        prune_mask |= full['scales'].max(axis=1) > f(np.log(0.1 * extent))                                                    # :362-363
+        prune_mask |= new['too_large']                                                                                        # :362-363
     keep = ~prune_mask                                                                                                        # :364 prune()
     new_p = {k: np.ascontiguousarray(full[k][keep]) for k in keys}
     new_m = new_v = None
