@@ -705,6 +705,81 @@ class Backend:
         self._check(self.lib.fgs_bilagrid_tv(grid.data_ptr(), *ext, loss.data_ptr(), _ptr(grad), _stream_of(device)), 'fgs_bilagrid_tv')
         return loss, grad
 
+    # -- normal-consistency regulariser (include/fgs_hip.h, csrc/normal_consistency.hip) ---------------------------------------------
+    @staticmethod
+    def _check_surface(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, w2c: torch.Tensor, cam_position: torch.Tensor,
+                       grad_features: Optional[torch.Tensor] = None) -> tuple:
+        """(device, N, w2c, cam_position as contiguous float32 tensors on the device) of the [N,3] / [N,3] / [N,4] tensors of a Gaussian set and a camera."""
+        tensors, names = [means, scales, rotations], ['means', 'scales', 'rotations']
+        if grad_features is not None:
+            tensors.append(grad_features); names.append('grad_features')
+        for t, name in zip(tensors, names):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != means.device:
+                raise RuntimeError(f"surface_features: '{name}' must be a contiguous float32 tensor on {means.device}")
+        n = means.shape[0]
+        if tuple(means.shape) != (n, 3) or tuple(scales.shape) != (n, 3) or tuple(rotations.shape) != (n, 4):
+            raise RuntimeError(f'surface_features: means, scales, rotations must be [N,3], [N,3], [N,4], got {tuple(means.shape)}, {tuple(scales.shape)}, '
+                               f'{tuple(rotations.shape)}')
+        if grad_features is not None and tuple(grad_features.shape) != (n, 5):
+            raise RuntimeError(f'surface_features: grad_features must be [N,5] = {(n, 5)}, got {tuple(grad_features.shape)}')
+        w2c = w2c.detach().to(device=means.device, dtype=torch.float32).contiguous()
+        cam = cam_position.detach().to(device=means.device, dtype=torch.float32).contiguous()
+        if w2c.dim() != 2 or w2c.shape[0] < 3 or w2c.shape[1] != 4 or cam.numel() != 3:
+            raise RuntimeError(f'surface_features: w2c must be [3,4] or [4,4] and cam_position have 3 entries, got {tuple(w2c.shape)}, {tuple(cam.shape)}')
+        return means.device, n, w2c, cam
+
+    def surface_features(self, means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, w2c: torch.Tensor, cam_position: torch.Tensor) -> torch.Tensor:
+        """[N,5] rows (n_cam, z, 1): the camera-space normal of every Gaussian (the axis of its smallest scale, turned towards the camera), the
+        view-space depth of its mean, and one -- the channels diff_rasterize_features blends into the map normal_consistency reads."""
+        device, n, w2c, cam = self._check_surface(means, scales, rotations, w2c, cam_position)
+        features = torch.empty((n, 5), dtype=torch.float32, device=device)
+        self._check(self.lib.fgs_surface_features(_ptr(means), _ptr(scales), _ptr(rotations), n, w2c.data_ptr(), cam.data_ptr(), _ptr(features),
+                                                  _stream_of(device)), 'fgs_surface_features')
+        return features
+
+    def surface_features_backward(self, means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, w2c: torch.Tensor, cam_position: torch.Tensor,
+                                  grad_features: torch.Tensor, need_rotations: bool = True, need_means: bool = True) -> tuple:
+        """(dL/drotations [N,4] or None, dL/dmeans [N,3] or None) for the upstream gradient of surface_features' output; a gradient that is not needed
+        is not computed. The scales get none (the choice of the axis and its sign are piecewise constant)."""
+        device, n, w2c, cam = self._check_surface(means, scales, rotations, w2c, cam_position, grad_features)
+        grad_rotations = torch.empty_like(rotations) if need_rotations else None
+        grad_means = torch.empty_like(means) if need_means else None
+        self._check(self.lib.fgs_surface_features_backward(_ptr(means), _ptr(scales), _ptr(rotations), n, w2c.data_ptr(), cam.data_ptr(), _ptr(grad_features),
+                                                           int(need_rotations), int(need_means), _ptr(grad_rotations), _ptr(grad_means), _stream_of(device)),
+                    'fgs_surface_features_backward')
+        return grad_rotations, grad_means
+
+    @staticmethod
+    def _check_surface_map(surface_map: torch.Tensor, settings: RasterizerSettings, grad: Optional[torch.Tensor] = None) -> tuple:
+        """(device, (W, H), (fx, fy, cx, cy)) of a [5,H,W] map of the settings' image size (and an upstream gradient [H,W])."""
+        for t, name in ((surface_map, 'surface_map'),) + (((grad, 'grad_consistency'),) if grad is not None else ()):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != surface_map.device:
+                raise RuntimeError(f"normal_consistency: '{name}' must be a contiguous float32 tensor on {surface_map.device}")
+        w, h = int(settings.width), int(settings.height)
+        if tuple(surface_map.shape) != (5, h, w) or surface_map.numel() == 0:
+            raise RuntimeError(f'normal_consistency: surface_map must be [5, H, W] = {(5, h, w)}, got {tuple(surface_map.shape)}')
+        if grad is not None and tuple(grad.shape) != (h, w):
+            raise RuntimeError(f'normal_consistency: grad_consistency must be [H, W] = {(h, w)}, got {tuple(grad.shape)}')
+        return surface_map.device, (w, h), (float(settings.focal_x), float(settings.focal_y), float(settings.center_x), float(settings.center_y))
+
+    def normal_consistency(self, surface_map: torch.Tensor, settings: RasterizerSettings, min_alpha: float = 0.5, return_normals: bool = False) -> tuple:
+        """(E [H,W], n_d [3,H,W] or None) of a blended map [5,H,W] = (N_r, D, A): E = A - N_r . n_d where the depth normal n_d exists, 0 elsewhere."""
+        device, size, intrinsics = self._check_surface_map(surface_map, settings)
+        E = torch.empty(surface_map.shape[1:], dtype=torch.float32, device=device)
+        normals = torch.empty((3, *surface_map.shape[1:]), dtype=torch.float32, device=device) if return_normals else None
+        self._check(self.lib.fgs_normal_consistency(surface_map.data_ptr(), *size, *intrinsics, float(min_alpha), E.data_ptr(), _ptr(normals),
+                                                    _stream_of(device)), 'fgs_normal_consistency')
+        return E, normals
+
+    def normal_consistency_backward(self, surface_map: torch.Tensor, grad_consistency: torch.Tensor, settings: RasterizerSettings,
+                                    min_alpha: float = 0.5) -> torch.Tensor:
+        """dL/dsurface_map [5,H,W] for the upstream gradient of E; every element is written, bit-reproducibly (a gather, no float atomics)."""
+        device, size, intrinsics = self._check_surface_map(surface_map, settings, grad_consistency)
+        grad_map = torch.empty_like(surface_map)
+        self._check(self.lib.fgs_normal_consistency_backward(surface_map.data_ptr(), grad_consistency.data_ptr(), *size, *intrinsics, float(min_alpha),
+                                                             grad_map.data_ptr(), _stream_of(device)), 'fgs_normal_consistency_backward')
+        return grad_map
+
     # -- Gaussian-sharded multi-GPU path (include/fgs_hip.h, "Gaussian-sharded multi-GPU path") --------------------------------
     def _settings_array(self, views: Sequence[RasterizerSettings], total_sh_rest: int, device: torch.device, keep: list):
         arr = (_lib.Settings * len(views))()

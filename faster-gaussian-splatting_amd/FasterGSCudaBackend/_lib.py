@@ -117,6 +117,10 @@ _SIGNATURES = {
     'fgs_bilagrid_slice_backward': (C.c_int32, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     'fgs_bilagrid_staged': (C.c_int32, [_I32] * 5),
     'fgs_bilagrid_tv': (C.c_int32, [_P, _I32, _I32, _I32, _P, _P, _P]),
+    'fgs_surface_features': (C.c_int32, [_P, _P, _P, _I32, _P, _P, _P, _P]),
+    'fgs_surface_features_backward': (C.c_int32, [_P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    'fgs_normal_consistency': (C.c_int32, [_P, _I32, _I32] + [C.c_float] * 5 + [_P, _P, _P]),
+    'fgs_normal_consistency_backward': (C.c_int32, [_P, _P, _I32, _I32] + [C.c_float] * 5 + [_P, _P]),
     'fgs_profile_enable': (C.c_int32, [_I32]),
     'fgs_profile_read': (C.c_int32, [C.POINTER(StageTime), _I32]),
     'fgs_debug_wave_selftest': (C.c_int32, [_P, _P]),

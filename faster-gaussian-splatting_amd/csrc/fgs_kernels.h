@@ -335,6 +335,25 @@ hipError_t launch_bilagrid_slice(const BilagridArgs& a, hipStream_t s);
 hipError_t launch_bilagrid_slice_backward(const BilagridArgs& a, float* grad_grid, hipStream_t s);   // grad_grid [12, L, Hg, Wg] is overwritten (with a.scratch)
 hipError_t launch_bilagrid_tv(const float* grid, int gw, int gh, int gl, float* loss, float* grad_grid, hipStream_t s);
 
+// normal_consistency.hip: the per-Gaussian surface features (n_cam, z, 1) and the image-space normal-consistency term over their blended map
+struct SurfaceFeatureArgs {
+    const float* means; const float* scales; const float* rotations;   // [N,3], [N,3] log-scales, [N,4] raw (r, x, y, z)
+    const float* w2c; const float* cam_position;                       // device: rows of four floats, rows 0..2 read; [3]
+    int n;
+    float* features;                                                   // forward: [N,5]
+    const float* grad_features; float* grad_rotations; float* grad_means;   // backward: upstream [N,5]; [N,4] / [N,3], each written in full, or nullptr = not wanted
+};
+struct NormalConsistencyArgs {
+    const float* map; int width, height;         // [5,H,W] = (N_r, D, A)
+    float inv_fx, inv_fy, cx, cy, min_alpha;
+    float* E; float* normals;                    // forward: [H,W]; n_d [3,H,W] or nullptr
+    const float* grad_E; float* grad_map;        // backward: upstream [H,W]; [5,H,W], every element written
+};
+hipError_t launch_surface_features(const SurfaceFeatureArgs& a, hipStream_t s);
+hipError_t launch_surface_features_backward(const SurfaceFeatureArgs& a, hipStream_t s);
+hipError_t launch_normal_consistency(const NormalConsistencyArgs& a, hipStream_t s);
+hipError_t launch_normal_consistency_backward(const NormalConsistencyArgs& a, hipStream_t s);
+
 // shard_exchange.hip: record (un)packing either side of the two exchanges of the Gaussian-sharded multi-GPU path
 struct PackRecordsView { const PrimRec* rec; const uint32_t* n_touched; const uint32_t* depth_keys; const uint32_t* prim_idx;
                          const uint32_t* counters; uint32_t* slot; uint32_t* out; uint32_t* counts_out; };

@@ -13,8 +13,8 @@ import math
 
 import torch
 
-from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_distortion, diff_rasterize_features, rasterize,
-                                 rasterize_aux)
+from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_distortion, diff_rasterize_features,
+                                 gaussian_surface_features, normal_consistency, rasterize, rasterize_aux)
 
 from .scenes import View
 
@@ -110,6 +110,17 @@ def render_image_training_distortion(g: Gaussians, view: View, update_densificat
                                      rasterizer_settings=extract_settings(view, g.active_sh_bases, bg_color), normalized=normalized)
 
 
+def render_image_training_normals(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, min_alpha: float = 0.5):
+    """render_image_training plus the differentiable normal-consistency map E = sum_i w_i (1 - n_i . n_d) per pixel (0 where the rendered depth gives no
+    normal): (image, E [H,W]). One diff_rasterize_features pass over the five surface channels (n_cam, z, 1) of gaussian_surface_features."""
+    settings = extract_settings(view, g.active_sh_bases, bg_color)
+    features = gaussian_surface_features(g.means, g.scales, g.rotations, view.w2c, view.position)
+    image, surface_map = diff_rasterize_features(*g.tensors(),
+                                                 densification_info=g.densification_info if update_densification_info else torch.empty(0),
+                                                 rasterizer_settings=settings, features=features, detach_geometry=False)
+    return image, normal_consistency(surface_map, settings, min_alpha=min_alpha)
+
+
 def depth_l1_loss(alpha: torch.Tensor, depth: torch.Tensor, depth_target: torch.Tensor, valid: 'torch.Tensor | None' = None) -> torch.Tensor:
     """L1 between the mean depth D / A.clamp_min(1e-8) and the target over the valid pixels (default: target > 0)."""
     valid = depth_target > 0 if valid is None else valid
@@ -161,7 +172,7 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
                        depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False,
                        bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0,
                        loss_weight: 'torch.Tensor | None' = None, distortion_weight: float = 0.0,
-                       distortion_normalized: bool = True) -> torch.Tensor:
+                       distortion_normalized: bool = True, normal_weight: float = 0.0, normal_min_alpha: float = 0.5) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
@@ -175,9 +186,14 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
     harness/loss.py; with a bilagrid the corrected image is what gets weighted). None (the default): loss_fn is called as before.
     distortion_weight > 0 adds distortion_weight * distortion.mean(), the depth-distortion regulariser of diff_rasterize_distortion (t normalized onto
     [0, 1) with the view's planes unless distortion_normalized=False). Not together with depth supervision or absgrad. 0 (the default): the step is
-    exactly the one without."""
+    exactly the one without.
+    normal_weight > 0 adds normal_weight * E.mean(), the normal-consistency regulariser of render_image_training_normals (pixels whose accumulated
+    opacity, or a neighbour's, is below normal_min_alpha add nothing). Not together with the distortion term, depth supervision or absgrad: each is a
+    different render. 0 (the default): the step is exactly the one without."""
     if distortion_weight > 0.0 and (absgrad or (depth_target is not None and depth_weight > 0.0)):
         raise ValueError('training_iteration: the distortion term does not combine with depth supervision or absgrad in one render')
+    if normal_weight > 0.0 and (distortion_weight > 0.0 or absgrad or (depth_target is not None and depth_weight > 0.0)):
+        raise ValueError('training_iteration: the normal-consistency term does not combine with the distortion term, depth supervision or absgrad in one render')
     if bilagrid is not None:
         loss_fn = bilagrid.corrected(loss_fn, view_index, tv_weight)
     if loss_weight is not None:
@@ -196,6 +212,10 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
         image, distortion = render_image_training_distortion(g, view, update_densification_info=iteration < densification_end,
                                                              bg_color=view.background_color, normalized=distortion_normalized)
         loss = loss_fn(image, target) + distortion_weight * distortion.mean()
+    elif normal_weight > 0.0:
+        image, consistency = render_image_training_normals(g, view, update_densification_info=iteration < densification_end,
+                                                           bg_color=view.background_color, min_alpha=normal_min_alpha)
+        loss = loss_fn(image, target) + normal_weight * consistency.mean()
     else:
         image = render_image_training(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color)
         loss = loss_fn(image, target)

@@ -561,6 +561,37 @@ int32_t fgs_bilagrid_staged(int32_t grid_w, int32_t grid_h, int32_t grid_l, int3
  * contributes 0): loss = one DEVICE float, grad_grid [12, L, Hg, Wg] = d tv / dG (overwritten) or NULL. One launch, sums in a fixed order. */
 int32_t fgs_bilagrid_tv(const float* grid, int32_t grid_w, int32_t grid_h, int32_t grid_l, float* loss, float* grad_grid, void* stream);
 
+/* ---- Normal-consistency regulariser of 2DGS, L_n = sum_i w_i (1 - n_i . N) (csrc/normal_consistency.hip; INTEGRATION.md "Normal consistency") ----
+ * Two pairs of calls either side of fgs_blend_features / fgs_backward_features over five channels. All tensors fp32, contiguous, on the current device;
+ * outputs caller-allocated; no host synchronisation, no allocation; all work on `stream`. Refused with FGS_ERR_INVALID_ARGUMENT and a text in
+ * fgs_last_error, before anything is written: a NULL required pointer, a negative n_primitives, a non-positive width / height / focal length, min_alpha
+ * outside (0, 1], rotations / grad_rotations that are not 16-byte aligned.
+ *
+ * Surface features: features [n_primitives, 5], row i = (n_cam, z_i, 1). k = index of the smallest of the three log-scales (the lowest index on an exact
+ * tie), a = column k of quat_to_rotation(rotations[i]) (raw (r, x, y, z), normalised inside), s = -1 if a . (means[i] - cam_position) > 0 else +1,
+ * n_cam = w2c[0:3,0:3] (s a), z_i = w2c[2,0:3] . means[i] + w2c[2,3]. w2c: rows of four floats, rows 0..2 read. n_primitives == 0 is valid (nothing is
+ * written; the per-Gaussian pointers may then be NULL). */
+int32_t fgs_surface_features(const float* means, const float* scales, const float* rotations, int32_t n_primitives, const float* w2c,
+                             const float* cam_position, float* features, void* stream);
+/* Gradients for an upstream grad_features [n_primitives, 5]: grad_rotations [n_primitives, 4] (through the rotation's normalisation) and grad_means
+ * [n_primitives, 3] (= grad_features[:, 3] w2c[2,0:3]), each written plainly in every row when its need_* flag is set and left alone (it may be NULL,
+ * it costs nothing) otherwise. No gradient for the scales (the choice of k and the sign are piecewise constant), none from channel 4. */
+int32_t fgs_surface_features_backward(const float* means, const float* scales, const float* rotations, int32_t n_primitives, const float* w2c,
+                                      const float* cam_position, const float* grad_features, int32_t need_rotations, int32_t need_means,
+                                      float* grad_rotations, float* grad_means, void* stream);
+/* Normal consistency of a blended map surface_map [5, height, width] = (N_r, D, A): with d = D / A, ray(q) = ((qx + 0.5 - center_x) / focal_x,
+ * (qy + 0.5 - center_y) / focal_y, 1), P = ray d, gx = P(p + (1,0)) - P(p - (1,0)), gy = P(p + (0,1)) - P(p - (0,1)), c = gy x gx, n_d = c / |c|:
+ * consistency[p] = A(p) - N_r(p) . n_d(p) where p is valid -- not on the image border, A >= min_alpha at p and at its four neighbours, |c|^2 > 1e-30 --
+ * and exactly 0 elsewhere (D / A is not formed there). normals [3, height, width]: n_d, zeros where invalid; NULL = not wanted. An image without an
+ * interior pixel (width or height < 3) is valid: the outputs are zero. */
+int32_t fgs_normal_consistency(const float* surface_map, int32_t width, int32_t height, float focal_x, float focal_y, float center_x, float center_y,
+                               float min_alpha, float* consistency, float* normals, void* stream);
+/* grad_map [5, height, width] for an upstream grad_consistency [height, width]; every element is written (zero where no valid pixel reaches it). The
+ * depth gradient is a gather -- the thread of a pixel recomputes the up to four valid centres it is a neighbour of -- without float atomics: two calls
+ * on the same inputs return the same bits. */
+int32_t fgs_normal_consistency_backward(const float* surface_map, const float* grad_consistency, int32_t width, int32_t height, float focal_x, float focal_y,
+                                        float center_x, float center_y, float min_alpha, float* grad_map, void* stream);
+
 /* Optional per-stage timing. While enabled (1), every pipeline stage is bracketed by hipEvents recorded on the caller's stream
  * (each event costs a few microseconds of GPU idle time: ~0.2 ms per training iteration with all stages on); enable = 2 + k brackets
  * only stage k (its index in the table fgs_profile_read returns), which leaves a timed loop practically undisturbed;
