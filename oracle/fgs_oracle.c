@@ -1,17 +1,17 @@
 /*
  * fgs_oracle.c -- CPU restatement of the FasterGS rasterizer hot path (TEST INFRASTRUCTURE ONLY).
  *
- * PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures for this path
- *  and its CUDA implementation cannot be compiled or run in this environment
- * (no nvcc, no NVIDIA device). This file restates the reference arithmetic from its sources; it is
- * pinned only by (a) an independent fp64 torch.autograd compositor (oracle/torch_check.py) and finite
- * differences of it, (b) hand-derived closed-form cases (one / two Gaussians on the optical axis: image
- * and analytic gradients) and the orthonormality of the SH basis, (c) structural invariants, (d) an fp64 render
- * BY DEFINITION (torch_check.py: brute_force_forward -- every Gaussian at every pixel under the per-pair alpha / transmittance
- * rules alone) for the discrete half: bounds, tile test, sub-tile test, sorts, lists, culls
- * (all in tests/test_oracle.py). None of these is an output of the reference itself. See DESIGN.md "Oracle".
- * (Round 6: the reference's Python glue -- torch_bindings/*.py -- IS executed in the build container and pinned by committed fixtures,
- * tests/golden/ref_glue_*; that pins the operator surface above the kernels, not the arithmetic restated in this file, which stays unpinned.)
+ * PINNED TO THE REFERENCE'S KERNELS AS WRITTEN: the reference's own torch-free host files and kernel headers are compiled for the CPU on the
+ * stand-in CUDA headers of oracle/cuda_on_cpu (oracle/build_ref.py, into the git-ignored oracle/_ref) and this file is held to them field by
+ * field: integers and indices exact, floats without atomics bit for bit, atomic sums within 1e-5 and with the same support
+ * (tests/test_reference_pin.py with a reference tree; tests/test_reference_fixtures.py against the committed tests/golden/ref_kernels_*.npz
+ * without one). Both sides are unfused fp32 on glibc, so what is pinned is the reference's arithmetic AS WRITTEN. NOT pinned: nvcc's FMA
+ * contraction and NVIDIA's __expf; the 32-bit-key path above 65 536 tiles; adam.cu and filter3d.cu (not built; orc_adam_step is held to
+ * torch.optim.Adam, the 3D filter to its fp64 model). Independent of the reference text the file is also held to (a) an fp64 torch.autograd
+ * compositor (oracle/torch_check.py) and finite differences of it, (b) hand-derived closed-form cases and the orthonormality of the SH basis,
+ * (c) structural invariants, (d) an fp64 render BY DEFINITION (torch_check.py: brute_force_forward) for the discrete half (all in
+ * tests/test_oracle.py). See DESIGN.md "Oracle".
+ * (The reference's Python glue -- torch_bindings/*.py -- is executed in the build container as well and pinned by tests/golden/ref_glue_*.)
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  * The product path (faster-gaussian-splatting_amd/) never links, imports or calls it.
@@ -1001,3 +1001,63 @@ void orc_pruning_scores(const uint* ranges, const uint* inst_prims, const uint16
     for (int i = 0; i < N; i++) scores[i] += (float)acc[i];
     free(acc);
 }
+
+#ifndef ORC_F64
+/* ---------------------------------------------------------------------------------------------------------------------------------------
+ * MCMC relocation and noise: densification/include/kernels_mcmc.cuh:10-57 and :69-127 in their order of operations (held bit for bit to the
+ * reference's own kernels run on the CPU, tests/test_reference_pin.py). The coefficient table is built in double as the host code there
+ * does: binom * sign * rsqrt(k + 1) with rsqrt(x) = 1 / sqrt(x), rounded to float once.
+ * --------------------------------------------------------------------------------------------------------------------------------------- */
+#define MCMC_MAX_N_SAMPLES 50
+void orc_relocation_adjustment(const float* old_opacities, const float* old_scales, const long long* n_samples_per_primitive, float* new_opacities,
+                               float* new_scales, int n_primitives) {
+    static float table[MCMC_MAX_N_SAMPLES * MCMC_MAX_N_SAMPLES];
+    memset(table, 0, sizeof(table));
+    for (int n = 0; n < MCMC_MAX_N_SAMPLES; n++) {
+        double binom = 1.0, sign = 1.0;
+        for (int k = 0; k <= n; k++, sign = -sign) {
+            table[n * MCMC_MAX_N_SAMPLES + k] = (float)(binom * sign * (1.0 / sqrt((double)(k + 1))));
+            binom *= (double)(n - k) / (double)(k + 1);
+        }
+    }
+    for (int i = 0; i < n_primitives; i++) {
+        const float old_opacity = old_opacities[i];
+        int n_samples = (int)n_samples_per_primitive[i];
+        n_samples = n_samples < 1 ? 1 : n_samples > MCMC_MAX_N_SAMPLES ? MCMC_MAX_N_SAMPLES : n_samples;
+        const float new_opacity = 1.0f - powf(1.0f - old_opacity, 1.0f / (float)n_samples);
+        new_opacities[i] = new_opacity;
+        float denominator = 0.0f;
+        for (int n = 0; n < n_samples; n++) {
+            float power = new_opacity;
+            for (int k = 0; k <= n; k++, power *= new_opacity) denominator += table[n * MCMC_MAX_N_SAMPLES + k] * power;
+        }
+        const float scaling_factor = old_opacity / denominator;
+        for (int c = 0; c < 3; c++) new_scales[3 * i + c] = scaling_factor * old_scales[3 * i + c];
+    }
+}
+
+void orc_add_noise(const float* raw_scales, const float* raw_rotations, const float* raw_opacities, const float* random_samples, float* means,
+                   int n_primitives, float current_lr) {
+    for (int i = 0; i < n_primitives; i++) {
+        const float vx = expf(2.0f * raw_scales[3 * i]), vy = expf(2.0f * raw_scales[3 * i + 1]), vz = expf(2.0f * raw_scales[3 * i + 2]);
+        const float r = raw_rotations[4 * i], x = raw_rotations[4 * i + 1], y = raw_rotations[4 * i + 2], z = raw_rotations[4 * i + 3];
+        const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, rx = r * x, ry = r * y, rz = r * z;
+        const float norm_sq = r * r + xx + yy + zz;
+        if (norm_sq < 1e-8f) continue;
+        const float rcp = 1.0f / norm_sq;
+        const float R[9] = {1.0f - 2.0f * (yy + zz) * rcp, 2.0f * (xy - rz) * rcp, 2.0f * (xz + ry) * rcp,
+                            2.0f * (xy + rz) * rcp, 1.0f - 2.0f * (xx + zz) * rcp, 2.0f * (yz - rx) * rcp,
+                            2.0f * (xz - ry) * rcp, 2.0f * (yz + rx) * rcp, 1.0f - 2.0f * (xx + yy) * rcp};
+        const float RSS[9] = {R[0] * vx, R[1] * vy, R[2] * vz, R[3] * vx, R[4] * vy, R[5] * vz, R[6] * vx, R[7] * vy, R[8] * vz};
+        const float c11 = RSS[0] * R[0] + RSS[1] * R[1] + RSS[2] * R[2], c12 = RSS[0] * R[3] + RSS[1] * R[4] + RSS[2] * R[5];
+        const float c13 = RSS[0] * R[6] + RSS[1] * R[7] + RSS[2] * R[8], c22 = RSS[3] * R[3] + RSS[4] * R[4] + RSS[5] * R[5];
+        const float c23 = RSS[3] * R[6] + RSS[4] * R[7] + RSS[5] * R[8], c33 = RSS[6] * R[6] + RSS[7] * R[7] + RSS[8] * R[8];
+        const float nx = random_samples[3 * i], ny = random_samples[3 * i + 1], nz = random_samples[3 * i + 2];
+        const float tx = c11 * nx + c12 * ny + c13 * nz, ty = c12 * nx + c22 * ny + c23 * nz, tz = c13 * nx + c23 * ny + c33 * nz;   /* helper_math dot */
+        const float opacity = 1.0f / (1.0f + expf(-raw_opacities[i]));
+        const float op_sigmoid = 1.0f / (1.0f + expf(100.0f * opacity - 0.5f));
+        const float noise_factor = current_lr * op_sigmoid;
+        means[3 * i] += noise_factor * tx; means[3 * i + 1] += noise_factor * ty; means[3 * i + 2] += noise_factor * tz;
+    }
+}
+#endif

@@ -1,6 +1,7 @@
 """ctypes front-end of the CPU oracle (oracle/fgs_oracle.c).  TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED (see fgs_oracle.c header): the reference has no golden vectors and cannot run here.
+Held to the reference's own kernels run on the CPU (oracle/reference.py, tests/test_reference_pin.py, tests/golden/ref_kernels_*.npz): see the
+fgs_oracle.c header for what that pins and what it does not.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the product
 package never does.
 
@@ -432,47 +433,23 @@ def update_3d_filter(positions, w2c, filter_3d, visibility_mask, width, height, 
 
 
 def relocation_adjustment(old_opacities, old_scales, n_samples_per_primitive):
-    """densification/include/kernels_mcmc.cuh:10-59 (Eq. 9 of 3DGS-MCMC), max 50 samples."""
-    f = np.float32
-    op, sc = _f32(old_opacities).reshape(-1), _f32(old_scales).reshape(-1, 3)
-    ns = np.clip(np.asarray(n_samples_per_primitive).astype(np.int64), 1, 50)
-    table = np.zeros((50, 50), np.float32)
-    for n in range(50):
-        binom, sign = 1.0, 1.0
-        for k in range(n + 1):
-            table[n, k] = f(binom * sign / np.sqrt(float(k + 1)))
-            binom *= (n - k) / (k + 1)
-            sign = -sign
-    new_op = (f(1.0) - np.power(f(1.0) - op, f(1.0) / ns.astype(np.float32))).astype(np.float32)
-    new_sc = np.zeros_like(sc)
-    for i in range(op.shape[0]):
-        den = f(0.0)
-        for n in range(int(ns[i])):
-            power = new_op[i]
-            for k in range(n + 1):
-                den = f(den + table[n, k] * power)
-                power = f(power * new_op[i])
-        new_sc[i] = (op[i] / den) * sc[i]
+    """densification/include/kernels_mcmc.cuh:10-57 (Eq. 9 of 3DGS-MCMC), max 50 samples: fgs_oracle.c orc_relocation_adjustment -- libm's powf and the
+    kernel's order of operations, bit-equal to the reference's kernel run on the CPU (the numpy restatement this replaces was one ulp off in the new
+    opacity, numpy's float32 power not being powf, which the cancelling denominator turned into 4e-5 of the new scales)."""
+    op, sc = np.ascontiguousarray(_f32(old_opacities).reshape(-1)), np.ascontiguousarray(_f32(old_scales).reshape(-1, 3))
+    ns = np.ascontiguousarray(np.asarray(n_samples_per_primitive).astype(np.int64).reshape(-1))
+    new_op, new_sc = np.zeros_like(op), np.zeros_like(sc)
+    lib().orc_relocation_adjustment(_p(op), _p(sc), _p(ns), _p(new_op), _p(new_sc), int(op.shape[0]))
     return new_op.reshape(-1, 1), new_sc
 
 
 def add_noise(raw_scales, raw_rotations, raw_opacities, random_samples, means, current_lr) -> None:
-    """densification/include/kernels_mcmc.cuh:69-127; `means` [N,3] float32 is updated in place."""
-    f = np.float32
-    s, q, o, r = _f32(raw_scales), _f32(raw_rotations), _f32(raw_opacities).reshape(-1), _f32(random_samples)
-    var = np.exp(f(2.0) * s)
-    rr, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-    nsq = rr * rr + x * x + y * y + z * z
-    ok = nsq >= f(1e-8)
-    inv = f(1.0) / np.where(ok, nsq, f(1.0))
-    R = np.stack([f(1) - f(2) * (y * y + z * z) * inv, f(2) * (x * y - rr * z) * inv, f(2) * (x * z + rr * y) * inv,
-                  f(2) * (x * y + rr * z) * inv, f(1) - f(2) * (x * x + z * z) * inv, f(2) * (y * z - rr * x) * inv,
-                  f(2) * (x * z - rr * y) * inv, f(2) * (y * z + rr * x) * inv, f(1) - f(2) * (x * x + y * y) * inv], 1).reshape(-1, 3, 3)
-    cov = (R * var[:, None, :]) @ R.transpose(0, 2, 1)
-    t = np.einsum('nij,nj->ni', cov, r).astype(np.float32)
-    opacity = f(1.0) / (f(1.0) + np.exp(-o))
-    factor = f(current_lr) * (f(1.0) / (f(1.0) + np.exp(f(100.0) * opacity - f(0.5))))
-    means[ok] += (factor[:, None] * t)[ok]
+    """densification/include/kernels_mcmc.cuh:69-127; `means` [N,3] float32 is updated in place. fgs_oracle.c orc_add_noise: the kernel's own order of
+    operations (a matmul's summation order is not the kernel's: 1.5e-6 of the displacement), bit-equal to the reference's kernel run on the CPU."""
+    assert means.dtype == np.float32 and means.flags['C_CONTIGUOUS']
+    s, q = np.ascontiguousarray(_f32(raw_scales).reshape(-1, 3)), np.ascontiguousarray(_f32(raw_rotations).reshape(-1, 4))
+    o, r = np.ascontiguousarray(_f32(raw_opacities).reshape(-1)), np.ascontiguousarray(_f32(random_samples).reshape(-1, 3))
+    lib().orc_add_noise(_p(s), _p(q), _p(o), _p(r), _p(means), int(means.shape[0]), C.c_float(current_lr))
 
 
 # ---- maintenance of the Gaussian set (SURVEY.md 8f rank 1), restated in numpy fp32 -------------------------------------------------

@@ -1,5 +1,5 @@
-"""Generates the committed golden fixtures from the CPU oracle (NOT from the reference, which cannot run here: no nvcc, no
-NVIDIA GPU -- "parity unpinned", see oracle/fgs_oracle.c). Run from the repo root:  python tests/golden/make_golden.py
+"""Generates the committed golden fixtures s0.npz / tiny_aa.npz from the CPU oracle (NOT from the reference: the fixtures its own kernels
+wrote are ref_kernels_*.npz, make_ref_kernel_golden.py). Run from the repo root:  python tests/golden/make_golden.py
 
 s0.npz : scene S0 (1 000 Gaussians, 128x128): inputs, every integer intermediate, image, T_final, the six
          gradients for a fixed grad_image, densification_info, and parameters/moments after 1 and 3 Adam steps.

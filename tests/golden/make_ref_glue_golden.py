@@ -14,7 +14,8 @@ is this repository's own code and only uses the public operator names; what land
 What this pins: rows a22 (_Rasterize glue), a29 (FusedAdam.step), a32 (RasterizerSettings) and the argument routing of every wrapper -- the
 package's own operators must reproduce the fixture bit for bit on the same simulation (tests/test_ref_glue.py) and within 1e-4 on the MI355X
 (tests/test_gpu_ref_glue.py). What it does NOT pin: the kernels' arithmetic -- both sides of the comparison run this repository's kernels
-(the reference's are CUDA-only); that remains "parity unpinned" (oracle/fgs_oracle.c header).
+here; that is pinned separately, by the reference's own kernels run on the CPU (tests/golden/make_ref_kernel_golden.py, oracle/fgs_oracle.c header,
+DESIGN.md section 4).
 
 Run from the repo root:  FGS_REFERENCE_TREE=<reference checkout> python tests/golden/make_ref_glue_golden.py
 It rewrites the fixtures in place; `git diff --stat tests/golden` afterwards is the check that the committed fixtures are what the reference's

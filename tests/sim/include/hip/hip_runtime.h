@@ -96,7 +96,8 @@ inline void trampoline() {
     abort();
 }
 
-inline void run_block(unsigned block_idx, unsigned block_dim, unsigned grid_dim, const std::function<void()>& body) {
+// Fresh fibers for one workgroup of `block_dim` work-items running `body` (shared with oracle/cuda_on_cpu, which schedules them itself).
+inline void init_block(unsigned block_idx, unsigned block_dim, unsigned grid_dim, const std::function<void()>& body) {
     Block& b = blk();
     constexpr size_t kStack = 128 * 1024;
     if (b.lanes.size() < block_dim) { b.lanes.resize(block_dim); b.stacks.resize(kStack * block_dim); }
@@ -114,6 +115,11 @@ inline void run_block(unsigned block_idx, unsigned block_dim, unsigned grid_dim,
         for (int r = 0; r < 6; ++r) *--sp = nullptr;
         L.sp = sp;
     }
+}
+
+inline void run_block(unsigned block_idx, unsigned block_dim, unsigned grid_dim, const std::function<void()>& body) {
+    init_block(block_idx, block_dim, grid_dim, body);
+    Block& b = blk();
     int alive = b.n;
     unsigned long stale_rounds = 0;
     while (alive > 0) {
