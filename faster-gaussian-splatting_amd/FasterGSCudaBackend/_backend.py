@@ -499,9 +499,77 @@ class Backend:
             _stream_of(device)), 'fgs_backward_distortion')
         return grads
 
+    @staticmethod
+    def _check_surface_features(surface_features: torch.Tensor, n: int, device: torch.device) -> None:
+        f = surface_features
+        if f.dim() != 2 or tuple(f.shape) != (n, 5) or f.dtype != torch.float32 or not f.is_contiguous() or f.device != device:
+            raise RuntimeError(f'surface_features must be a contiguous float32 [N, 5] = [{n}, 5] tensor on the device of the forward pass, not '
+                               f'{tuple(f.shape)} {f.dtype} on {f.device}')
+
+    def blend_geometry(self, means: torch.Tensor, surface_features: torch.Tensor, result, n_primitives: int, settings: RasterizerSettings,
+                       normalized: bool = True) -> torch.Tensor:
+        """fgs_blend_geometry: the state [8,H,W] of the one walk that carries the depth-distortion map and the blend of five per-Gaussian channels over
+        the pairs the training blend of `result` (a synchronous forward / forward_aux over `n_primitives` Gaussians with these means and settings)
+        blended. Plane 0 is `blend_distortion`'s map X (same `normalized`), state[2:7] is `blend_features`' map of `surface_features` [N, 5], a
+        contiguous [5,H,W] that `normal_consistency` takes as it is; planes 1 and 7 are `backward_geometry`'s."""
+        device = result.image.device
+        n = int(n_primitives)
+        self._check_distortion_means(means, n, device)
+        self._check_surface_features(surface_features, n, device)
+        keep: list = []
+        S = self._settings(settings, int(settings.active_sh_bases) - 1, device, keep)      # the blend reads no SH coefficient: any consistent count
+        st = _lib.ForwardState(*result.state)
+        gstate = torch.empty((8, int(settings.height), int(settings.width)), dtype=torch.float32, device=device)
+        b = result.buffers
+        self._check(self.lib.fgs_blend_geometry(_ptr(means), _ptr(surface_features), _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), n, C.byref(S), C.byref(st),
+                                                _lib.DISTORTION_NORMALIZED if normalized else _lib.DISTORTION_LINEAR, gstate.data_ptr(),
+                                                _stream_of(device)), 'fgs_blend_geometry')
+        return gstate
+
+    def backward_geometry(self, densification_info, grad_image, grad_distortion, grad_surface_map, image, geometry_state, surface_features, means,
+                          scales, rotations, opacities, sh_rest, buffers, settings, state, normalized: bool = True,
+                          live_blocks: Optional[torch.Tensor] = None, reached_blocks: Optional[torch.Tensor] = None) -> tuple:
+        """fgs_backward_geometry: the six gradients of `backward` plus grad_surface_features [N, 5], for a loss that also depends on plane 0 and / or
+        planes 2..6 of `blend_geometry`'s state (same `normalized`, same features). grad_distortion [H,W] and grad_surface_map [5,H,W], either or
+        both None: both None is `backward` exactly and the seventh result is None. Gradients come back in fresh tensors."""
+        if grad_distortion is None and grad_surface_map is None:
+            return self.backward(densification_info, grad_image, image, means, scales, rotations, opacities, sh_rest, buffers, settings, state,
+                                 live_blocks=live_blocks, reached_blocks=reached_blocks) + (None,)
+        device = self._check_params((means, scales, rotations, opacities, sh_rest), BACKWARD_PARAMETER_NAMES)
+        n = means.shape[0]
+        hw = (int(settings.height), int(settings.width))
+        self._check_surface_features(surface_features, n, device)
+        if grad_distortion is not None and (tuple(grad_distortion.shape) != hw or grad_distortion.device != device):
+            raise RuntimeError(f'grad_distortion must be a [H,W] = {hw} tensor on the parameters\' device')
+        if grad_surface_map is not None and (tuple(grad_surface_map.shape) != (5,) + hw or grad_surface_map.device != device):
+            raise RuntimeError(f'grad_surface_map must be a [5,H,W] = {(5,) + hw} tensor on the parameters\' device')
+        if tuple(geometry_state.shape) != (8,) + hw or geometry_state.device != device:
+            raise RuntimeError(f'geometry_state must be the [8,H,W] = {(8,) + hw} tensor blend_geometry returned')
+        geometry_state = geometry_state.to(dtype=torch.float32).contiguous()
+        grad_distortion = grad_distortion.to(dtype=torch.float32).contiguous() if grad_distortion is not None else None
+        grad_surface_map = grad_surface_map.to(dtype=torch.float32).contiguous() if grad_surface_map is not None else None
+        grad_image = grad_image.to(dtype=torch.float32).contiguous()
+        keep: list = []
+        total_rest = total_sh_rest(sh_rest)
+        S = self._settings(settings, total_rest, device, keep)
+        grads = _gradients_out(None, gradient_shapes(n, total_rest), device)
+        grad_features = torch.empty((n, 5), dtype=torch.float32, device=device)
+        dens = _densification(densification_info, n, device, validate=True)
+        _check_block_flags('live_blocks', live_blocks, n, device)
+        _check_block_flags('reached_blocks', reached_blocks, n, device)
+        scratch = self._scratch_aux(n, settings, device)                # dL/dz of the distortion term lives in the aux layout's acc_z
+        st = _lib.ForwardState(*state)
+        self._check(self.lib.fgs_backward_geometry(
+            _ptr(grad_image), _ptr(image), None, None, None, _ptr(means), _ptr(scales), _ptr(rotations), _ptr(opacities), _ptr(sh_rest),
+            _ptr(buffers[0]), _ptr(buffers[1]), _ptr(buffers[2]), _ptr(buffers[3]), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
+            _ptr(grads[4]), _ptr(grads[5]), _ptr(dens), scratch.data_ptr(), n, C.byref(S), C.byref(st), _ptr(live_blocks), _ptr(reached_blocks),
+            _ptr(surface_features), _ptr(geometry_state), _ptr(grad_distortion), _ptr(grad_surface_map), _ptr(grad_features),
+            _lib.DISTORTION_NORMALIZED if normalized else _lib.DISTORTION_LINEAR, _stream_of(device)), 'fgs_backward_geometry')
+        return grads + (grad_features,)
+
     def backward_adam_fused(self, densification_info, grad_image, image, params: Sequence[torch.Tensor], exp_avgs, exp_avg_sqs,
                             buffers, settings, state, step: int, lrs: Sequence[float], betas=(0.9, 0.999), eps: float = 1e-15,
-                            grad_alpha=None, grad_depth=None, grad_feature_map=None, grad_distortion=None) -> None:
+                            grad_alpha=None, grad_depth=None, grad_feature_map=None, grad_distortion=None, grad_geometry=None) -> None:
         """params / moments / lrs in optimizer-group order: means, sh0, sh_rest, opacities, scales, rotations (Model.py:238-245)."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_adam_fused takes no alpha / depth gradients: use backward_aux and an optimizer step of its own')
@@ -509,6 +577,8 @@ class Backend:
             raise RuntimeError('backward_adam_fused takes no feature-map gradient: use backward_features and an optimizer step of its own')
         if grad_distortion is not None:
             raise RuntimeError('backward_adam_fused takes no distortion gradient: use backward_distortion and an optimizer step of its own')
+        if grad_geometry is not None:
+            raise RuntimeError('backward_adam_fused takes no geometry gradient: use backward_geometry and an optimizer step of its own')
         device = self._check_params(tuple(params) + tuple(exp_avgs) + tuple(exp_avg_sqs), ['param/moment'] * 18)
         keep: list = []
         n = params[0].shape[0]
@@ -821,7 +891,7 @@ class Backend:
 
     def backward_to_records(self, grad_image, image, buffers, settings: RasterizerSettings, state, total_sh_rest: int,
                             out: torch.Tensor | None = None, shard_counts: Sequence[int] | None = None, grad_alpha=None, grad_depth=None,
-                            grad_feature_map=None, grad_distortion=None) -> torch.Tensor:
+                            grad_feature_map=None, grad_distortion=None, grad_geometry=None) -> torch.Tensor:
         """K11 of a view rendered by `forward_from_records` -> float32 [n_records, 9] accumulator records."""
         if grad_alpha is not None or grad_depth is not None:
             raise RuntimeError('backward_to_records takes no alpha / depth gradients: the sharded and record paths render colour only')
@@ -829,6 +899,8 @@ class Backend:
             raise RuntimeError('backward_to_records takes no feature-map gradient: the sharded and record paths render colour only')
         if grad_distortion is not None:
             raise RuntimeError('backward_to_records takes no distortion gradient: the sharded and record paths render colour only')
+        if grad_geometry is not None:
+            raise RuntimeError('backward_to_records takes no geometry gradient: the sharded and record paths render colour only')
         device = image.device
         n = int(state[0])
         keep: list = []

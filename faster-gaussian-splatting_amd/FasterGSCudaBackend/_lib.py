@@ -68,6 +68,9 @@ _SIGNATURES = {
     'fgs_blend_distortion': (C.c_int32, [_P, _P, _P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _I32, _P, _P]),
     'fgs_backward_distortion': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P,
                                             _P, _P, _I32, _P]),
+    'fgs_blend_geometry': (C.c_int32, [_P, _P, _P, _P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _I32, _P, _P]),
+    'fgs_backward_geometry': (C.c_int32, [_P] * 5 + [_P] * 5 + [_P] * 4 + [_P] * 6 + [_P, _P, _I32, C.POINTER(Settings), C.POINTER(ForwardState), _P, _P,
+                                          _P, _P, _P, _P, _P, _I32, _P]),
     'fgs_forward_async': (C.c_int32, [_P] * 6 + [_I32, C.POINTER(Settings), _P, _I32, RESIZE_FN, _P, C.POINTER(ForwardState), _P]),
     'fgs_forward_counts': (C.c_int32, [_P, _I32, _P, _P]),
     'fgs_backward_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),

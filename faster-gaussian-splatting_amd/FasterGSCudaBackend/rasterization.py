@@ -695,6 +695,57 @@ def diff_rasterize_distortion(means: torch.Tensor, scales: torch.Tensor, rotatio
                                       rasterizer_settings, bool(normalized))
 
 
+class _RasterizeGeometry(torch.autograd.Function):
+    """_Rasterize that also returns, from ONE extra walk, the depth-distortion map and the blend of five per-Gaussian surface channels of the same pass,
+    differentiable in the Gaussians and in the channels (fgs_blend_geometry / fgs_backward_geometry). Always the synchronous forward pass; gradients in
+    fresh tensors (no arena, no live-block hand-over)."""
+
+    @staticmethod
+    def forward(ctx: Any, means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, surface_features,
+                rasterizer_settings: RasterizerSettings, normalized: bool):
+        _require_gpu(means)
+        be = default_backend()
+        res = be.forward(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, rasterizer_settings)
+        state = be.blend_geometry(means, surface_features, res, means.shape[0], rasterizer_settings, normalized)
+        ctx.rasterizer_settings = rasterizer_settings
+        ctx.buffer_state = res.state
+        ctx.normalized = bool(normalized)
+        ctx.set_materialize_grads(False)          # an output the loss does not use arrives as None (= zero), not as a tensor of zeros
+        ctx.save_for_backward(res.image, state, surface_features, means, scales, rotations, opacities, sh_coefficients_rest, *res.buffers)
+        ctx.densification_info = densification_info
+        ctx.mark_non_differentiable(densification_info)
+        return res.image, state[0], state[2:7]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx: Any, grad_image, grad_distortion, grad_surface_map):
+        image, state, surface_features, means, scales, rotations, opacities, sh_rest, *buffers = ctx.saved_tensors
+        if grad_image is None:
+            grad_image = torch.zeros_like(image)
+        clear_live_blocks([means])
+        # a map that is not part of the loss costs nothing: its sums are not formed, and with neither the pass is the plain one
+        *grads, grad_features = default_backend().backward_geometry(
+            ctx.densification_info, grad_image.contiguous(), grad_distortion.contiguous() if grad_distortion is not None else None,
+            grad_surface_map.contiguous() if grad_surface_map is not None else None, image, state, surface_features,
+            means, scales, rotations, opacities, sh_rest, buffers, ctx.rasterizer_settings, ctx.buffer_state, ctx.normalized)
+        return (*grads, None, grad_features if ctx.needs_input_grad[7] else None, None, None)
+
+
+def diff_rasterize_geometry(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
+                            sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, densification_info: torch.Tensor,
+                            rasterizer_settings: RasterizerSettings, surface_features: torch.Tensor, normalized: bool = True):
+    """Training render that also returns, differentiable and from one extra walk forward and one backward, what the geometry terms of 2DGS-style
+    training need: (image [3,H,W], distortion [H,W], surface_map [5,H,W]). distortion is diff_rasterize_distortion's map (same `normalized`);
+    surface_map[c] = sum_i w_i surface_features[i, c] is diff_rasterize_features' map of `surface_features`, float32 [N, 5] -- for
+    `gaussian_surface_features` the blended normal (0..2), the expected depth (3) and the accumulated opacity (4), which `normal_consistency` takes as
+    it is and a depth loss reads as surface_map[3], surface_map[4]. An output the loss does not use costs nothing in the backward pass; with neither
+    map in the loss that pass is diff_rasterize's. The image is diff_rasterize's. No gradient for the planes."""
+    if surface_features.dtype != torch.float32 or not surface_features.is_contiguous():          # the shape is the backend's to refuse
+        surface_features = surface_features.to(torch.float32).contiguous()
+    return _RasterizeGeometry.apply(means, scales, rotations, opacities, sh_coefficients_0, sh_coefficients_rest, densification_info, surface_features,
+                                    rasterizer_settings, bool(normalized))
+
+
 def rasterize(means: torch.Tensor, scales: torch.Tensor, rotations: torch.Tensor, opacities: torch.Tensor,
               sh_coefficients_0: torch.Tensor, sh_coefficients_rest: torch.Tensor, rasterizer_settings: RasterizerSettings,
               to_chw: bool, clamp_output: bool = True) -> torch.Tensor:

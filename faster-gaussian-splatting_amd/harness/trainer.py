@@ -14,7 +14,7 @@ import math
 import torch
 
 from FasterGSCudaBackend import (FusedAdam, RasterizerSettings, diff_rasterize, diff_rasterize_absgrad, diff_rasterize_aux, diff_rasterize_distortion, diff_rasterize_features,
-                                 gaussian_surface_features, normal_consistency, rasterize, rasterize_aux)
+                                 diff_rasterize_geometry, gaussian_surface_features, normal_consistency, rasterize, rasterize_aux)
 
 from .scenes import View
 
@@ -121,6 +121,20 @@ def render_image_training_normals(g: Gaussians, view: View, update_densification
     return image, normal_consistency(surface_map, settings, min_alpha=min_alpha)
 
 
+def render_image_training_geometry(g: Gaussians, view: View, update_densification_info: bool, bg_color: torch.Tensor, normalized: bool = True,
+                                   min_alpha: float = 0.5):
+    """render_image_training plus every geometry term of 2DGS-style training from ONE diff_rasterize_geometry pass over the five surface channels of
+    gaussian_surface_features: (image, distortion [H,W], E [H,W], alpha [H,W], depth [H,W]) -- the depth-distortion map of
+    render_image_training_distortion, the normal-consistency map of render_image_training_normals, and the accumulated opacity and expected depth of
+    render_image_training_aux (channels 4 and 3 of the surface map), all differentiable. A term the loss does not use costs nothing backward."""
+    settings = extract_settings(view, g.active_sh_bases, bg_color)
+    features = gaussian_surface_features(g.means, g.scales, g.rotations, view.w2c, view.position)
+    image, distortion, surface_map = diff_rasterize_geometry(*g.tensors(),
+                                                             densification_info=g.densification_info if update_densification_info else torch.empty(0),
+                                                             rasterizer_settings=settings, surface_features=features, normalized=normalized)
+    return image, distortion, normal_consistency(surface_map, settings, min_alpha=min_alpha), surface_map[4], surface_map[3]
+
+
 def depth_l1_loss(alpha: torch.Tensor, depth: torch.Tensor, depth_target: torch.Tensor, valid: 'torch.Tensor | None' = None) -> torch.Tensor:
     """L1 between the mean depth D / A.clamp_min(1e-8) and the target over the valid pixels (default: target > 0)."""
     valid = depth_target > 0 if valid is None else valid
@@ -172,7 +186,8 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
                        depth_weight: float = 0.0, depth_valid: 'torch.Tensor | None' = None, absgrad: bool = False,
                        bilagrid=None, view_index: 'int | None' = None, tv_weight: float = 10.0,
                        loss_weight: 'torch.Tensor | None' = None, distortion_weight: float = 0.0,
-                       distortion_normalized: bool = True, normal_weight: float = 0.0, normal_min_alpha: float = 0.5) -> torch.Tensor:
+                       distortion_normalized: bool = True, normal_weight: float = 0.0, normal_min_alpha: float = 0.5,
+                       geometry_render: bool = False) -> torch.Tensor:
     """One optimisation step in the reference's order (Trainer.py:170-199): lr update -> render -> loss -> backward ->
     optimizer.step -> zero_grad. `before_step` (if given) runs between backward and step (gradient exchange hook).
     depth_target [H,W] with depth_weight > 0 adds depth_weight * L1(D / A, depth_target) over the valid pixels (depth_valid, default target > 0):
@@ -189,10 +204,15 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
     exactly the one without.
     normal_weight > 0 adds normal_weight * E.mean(), the normal-consistency regulariser of render_image_training_normals (pixels whose accumulated
     opacity, or a neighbour's, is below normal_min_alpha add nothing). Not together with the distortion term, depth supervision or absgrad: each is a
-    different render. 0 (the default): the step is exactly the one without."""
-    if distortion_weight > 0.0 and (absgrad or (depth_target is not None and depth_weight > 0.0)):
+    different render. 0 (the default): the step is exactly the one without.
+    geometry_render=True: the distortion term, the normal-consistency term and depth supervision may all be active in one call and all come from the
+    ONE render of render_image_training_geometry: the loss is loss_fn's plus distortion_weight * distortion.mean(), normal_weight * E.mean() and
+    depth_weight * depth_l1_loss(alpha, depth, ...), each where its weight is positive. Not together with absgrad. False (the default): nothing changes."""
+    if geometry_render and absgrad:
+        raise ValueError('training_iteration: the geometry render does not combine with absgrad in one render')
+    if not geometry_render and distortion_weight > 0.0 and (absgrad or (depth_target is not None and depth_weight > 0.0)):
         raise ValueError('training_iteration: the distortion term does not combine with depth supervision or absgrad in one render')
-    if normal_weight > 0.0 and (distortion_weight > 0.0 or absgrad or (depth_target is not None and depth_weight > 0.0)):
+    if not geometry_render and normal_weight > 0.0 and (distortion_weight > 0.0 or absgrad or (depth_target is not None and depth_weight > 0.0)):
         raise ValueError('training_iteration: the normal-consistency term does not combine with the distortion term, depth supervision or absgrad in one render')
     if bilagrid is not None:
         loss_fn = bilagrid.corrected(loss_fn, view_index, tv_weight)
@@ -201,7 +221,18 @@ def training_iteration(g: Gaussians, view: View, target: torch.Tensor, iteration
         loss_fn = lambda image, target: unweighted_fn(image, target, weight=loss_weight)
     g.update_learning_rate(iteration + 1)
     with_depth = depth_target is not None and depth_weight > 0.0
-    if absgrad:
+    if geometry_render:
+        image, distortion, consistency, alpha, depth = render_image_training_geometry(
+            g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color, normalized=distortion_normalized,
+            min_alpha=normal_min_alpha)
+        loss = loss_fn(image, target)
+        if distortion_weight > 0.0:
+            loss = loss + distortion_weight * distortion.mean()
+        if normal_weight > 0.0:
+            loss = loss + normal_weight * consistency.mean()
+        if with_depth:
+            loss = loss + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid)
+    elif absgrad:
         image, alpha, depth = render_image_training_absgrad(g, view, update_densification_info=iteration < densification_end, bg_color=view.background_color,
                                                             alpha=with_depth, depth=with_depth)
         loss = loss_fn(image, target) + depth_weight * depth_l1_loss(alpha, depth, depth_target, depth_valid) if with_depth else loss_fn(image, target)

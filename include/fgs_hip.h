@@ -283,6 +283,41 @@ int32_t fgs_backward_distortion(const float* grad_image, const float* image, con
                                 int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
                                 uint8_t* reached_blocks, const float* distortion_state, const float* grad_distortion, int32_t mode, void* stream);
 
+/* One render for the 2DGS regularisers of the training pass: the depth-distortion map X of fgs_blend_distortion (same `mode`, same t) and the blend
+ * M_c = sum_i w_i surface_features[i][c] of fgs_blend_features for FIVE channels, over the same pairs in ONE walk. surface_features: fp32
+ * [n_primitives, 5] contiguous, any sign -- for the normal-consistency term what fgs_surface_features wrote: the view-space normal, the depth z and a
+ * one, so that M[3] is the expected depth and M[4] the accumulated opacity.
+ * geometry_state: fp32 [8, H, W], every element written. Plane 0 is X, exactly 0 where fewer than two Gaussians were blended; planes 2..6 are M, a
+ * contiguous [5, H, W] that fgs_normal_consistency takes as its surface_map as it is; planes 1 (sum w (t - t0 of the tile)) and 7 (sum w) are what
+ * fgs_backward_geometry needs and are the library's private format. X does not read channel 4: it equals fgs_blend_distortion's whatever the channels hold.
+ * Buffers and `state`: as for fgs_blend_distortion. FGS_ERR_INVALID_ARGUMENT, never ignored: a mode other than the two, near_plane <= 0 or far_plane <=
+ * near_plane in normalized mode, NULL geometry_state, NULL means or surface_features (n_primitives > 0), buffers of fgs_forward_async or of the record /
+ * sharded forward passes. n_primitives == 0: a zero state, nothing else is written. */
+int32_t fgs_blend_geometry(const float* means, const float* surface_features, const void* primitive_buffers, const void* tile_buffers,
+                           const void* instance_buffers, int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, int32_t mode,
+                           float* geometry_state, void* stream);
+/* fgs_backward_reached for a loss that also depends on X and / or M: geometry_state = what fgs_blend_geometry wrote (same mode and features),
+ * grad_distortion = the upstream gradient of plane 0 [H, W], grad_surface_map = that of planes 2..6 [5, H, W]; either may be NULL (= zero, and its sums
+ * are not formed). dL/dalpha is linear in them, so one walk serves both: with e_i of fgs_backward_distortion, u_i of fgs_backward_features,
+ * c_i = gX e_i + u_i and S_i = gX 2 X + sum_c M_c gM_c - sum_{j<=i} w_j c_j,
+ *     dL/dalpha_i(p)           += T_i c_i - S_i / max(1 - alpha_i, 1e-6)               added to the colour term's per-Gaussian sums, then K12 as always
+ *     dL/dz_i                   = sum_p gX 2 w_i (2 A_{i-1} + w_i - A_n) dt_i/dz_i      grad_means[i] += dL/dz_i w2c[2, 0:3] behind K12
+ *     grad_surface_features[i][c] = sum_p w_i gM_c(p)                                  fp32 [n_primitives, 5], zeroed by the call
+ * The kernels run K11, the geometry backward blend, K12, the depth term of the means. scratch: fgs_backward_aux_scratch_bytes, with or without map
+ * gradients. Both upstream gradients NULL IS fgs_backward_reached: the geometry arguments are not looked at and the scratch is that pass's. Refused like
+ * fgs_blend_geometry, and NULL geometry_state / surface_features / grad_surface_features; the fused backward + Adam, asynchronous, sharded and record
+ * paths and the pose and absgrad entry points take no geometry gradient. No gradient for near_plane / far_plane. n_primitives == 0 writes nothing. */
+int32_t fgs_backward_geometry(const float* grad_image, const float* image, const float* grad_alpha, const float* grad_depth, const float* depth_expected,
+                              const float* means, const float* scales, const float* rotations, const float* opacities,
+                              const float* sh_coefficients_rest,
+                              void* primitive_buffers, void* tile_buffers, void* instance_buffers, void* bucket_buffers,
+                              float* grad_means, float* grad_scales, float* grad_rotations, float* grad_opacities,
+                              float* grad_sh_coefficients_0, float* grad_sh_coefficients_rest,
+                              float* densification_info, void* scratch,
+                              int32_t n_primitives, const fgs_settings* settings, const fgs_forward_state* state, uint8_t* live_blocks,
+                              uint8_t* reached_blocks, const float* surface_features, const float* geometry_state, const float* grad_distortion,
+                              const float* grad_surface_map, float* grad_surface_features, int32_t mode, void* stream);
+
 /* fgs_forward WITHOUT its host synchronisation (the reference blocks three times per forward pass, forward.cu:100,102,234; fgs_forward
  * once): nothing is read back. The instance-stage buffers and launches are sized by `instance_capacity` -- the caller's bound, e.g. 1.25 x
  * the largest count fgs_forward_counts() has reported, scaled with the primitive count -- and every kernel reads the exact counts on the
