@@ -30,6 +30,7 @@ int32_t fgs_debug_set_option(int32_t key, int32_t value) {
         case 14: if (value < 1) return fail(FGS_ERR_INVALID_ARGUMENT, "the chained K11 needs at least one wave"); fgs::g_k11_chain_waves = value; return FGS_OK;
         case 15: if (value < 1 || value > 32) return fail(FGS_ERR_INVALID_ARGUMENT, "the Adam span must be 1..32 chunks of 1024 floats");
                  fgs::g_adam_span = value; return FGS_OK;
+        case 16: fgs::g_loss_form = value & 3; return FGS_OK;
         case 5: if (value < 0 || value > 32) return fail(FGS_ERR_INVALID_ARGUMENT, "seq_tiles must be 0 (flattened counting) or 1..32");
                 g_seq_tiles = value; return FGS_OK;
         default: return fail(FGS_ERR_INVALID_ARGUMENT, "unknown option %d", key);

@@ -17,13 +17,13 @@ struct AdcScratch {
     }
 };
 
-// The loss scratch, in floats: three derivative maps [3,H,W] of plane3 each, then the per-workgroup partial sums on an 8-byte boundary (read as
-// float2: 9 W H is odd for odd x odd images)
+// The loss scratch, in floats: three derivative maps [3,H,W] of plane3 each, then the forward kernel's partial sums -- one pair per wave, i.e. per
+// strip of 64 columns and band of rows of a channel (l1_dssim_partials) -- on an 8-byte boundary (read as float2: 9 W H is odd for odd x odd images)
 struct LossScratch {
     size_t plane3, partials_at;
     LossScratch(int width, int height) : plane3(3 * static_cast<size_t>(width) * static_cast<size_t>(height)), partials_at((3 * plane3 + 1) & ~static_cast<size_t>(1)) {}
     void point_maps(LossArgs& a, void* scratch) const { a.d_mu = static_cast<float*>(scratch); a.d_m11 = a.d_mu + plane3; a.d_m12 = a.d_m11 + plane3; }
-    // the weighted loss appends the tiles' weight sums and their total S to the same layout
+    // the weighted loss appends the strip-bands' weight sums (one channel plane's worth) and their total S to the same layout
     void point_weighted(LossArgs& a, void* scratch, const float* weight, int width, int height) const {
         point_maps(a, scratch);
         a.weight = weight; a.partials = a.d_mu + partials_at; a.wpartials = a.partials + l1_dssim_partials(width, height);

@@ -87,6 +87,7 @@ FGS_SWITCH(g_depth_sort_mode, 1);                    // sort_exhibits.hip, optio
 FGS_SWITCH(g_adam_reverse, 1);                       // adam.hip (launch_adam_exhibit), option 8: reversed workgroup order
 FGS_SWITCH(g_adam_nontemporal, 1);                   // same, option 2: non-temporal loads / stores
 FGS_SWITCH(g_adam_unroll, 1);                        // same, option 1: 1, 2 or 4 float4 pieces per thread (plain loads / stores only)
+FGS_SWITCH(g_loss_form, 0);                          // loss_exhibits.hip, option 16 -- bit 0: the tiled forward loss kernel, bit 1: the tiled backward one; 0 = the product's streaming kernels
 #endif
 FGS_SWITCH(g_fused_single_kernel, 1);                // option 3: K12 / fused K12+K13 of the single-GPU path as one kernel (1) or as round 1's two (0)
 FGS_SWITCH(g_adam_span, 1);                          // adam.hip, option 15: chunks a workgroup of K13 walks one after the other, 1..32 (above 1: costed and not built, profiles/adam_spans.txt)
@@ -307,13 +308,13 @@ struct LossArgs {                       // fused L1 + DSSIM loss and its image g
     float* sums;                                 // [0] sum |x-y|, [1] sum SSIM   (zeroed by the host before the launch)
     float* grad;                                 // [3,H,W] or nullptr
     float* d_mu; float* d_m11; float* d_m12;     // scratch derivative maps, [3,H,W] each
-    float* partials;                             // scratch: 2 floats per workgroup of the forward kernel
+    float* partials;                             // scratch: 2 floats per wave (strip-band) of the forward kernel
     int width, height;
     float lambda_l1, lambda_dssim;
     const float* upstream;                       // device scalar dL/dloss the gradient is multiplied with, or nullptr (= 1)
     // the weighted loss (INTEGRATION.md 'Weighted loss'); all three nullptr for the unweighted one
     const float* weight;                         // [H,W] per-pixel weights shared by the channels: w > 0 counts as w, anything else (0, negative, NaN) as 0
-    float* wpartials;                            // scratch: the sum of the effective weights of every forward tile, one float per tile of ONE channel plane
+    float* wpartials;                            // scratch: the sum of the effective weights of every strip-band of the forward kernel, one float per strip-band of ONE channel plane
     float* total_weight;                         // scratch: S, their sum in a fixed order (written by the reduction, read by the backward kernel)
 };
 size_t l1_dssim_partials(int width, int height);   // number of floats in LossArgs::partials

@@ -672,8 +672,10 @@ int32_t fgs_debug_set_backward_variant(int32_t variant);
  * contiguous band of tile rows per XCD (rounds 1-2), g = 1..64 = groups of g rows dealt to the XCDs in turn, 255 = the bands walked
  * bottom-up, 254 = blocks of tiles weighed and dealt to the XCDs on the device (plan_tiles_kernel), 253 = the bands read through the plan
  * table (csrc/fgs_k10_mappings.h has the measurements; the product library always runs 252), 11 = 1: rocPRIM scan for the per-tile bucket offsets (and no block plan), 12 = 1: the
- * block plan without sorting (XCD x = block column x), 13 = upper bound of the grid of blend-backward variant 4.
- * Apart from key 7, results never depend on them. */
+ * block plan without sorting (XCD x = block column x), 13 = upper bound of the grid of blend-backward variant 4, 16 = loss kernels: bit 0 the tiled
+ * forward kernel, bit 1 the tiled backward kernel of csrc/loss_exhibits.hip (0 default: the streaming kernels of csrc/loss.hip).
+ * Apart from key 7, results never depend on them (key 16: derivative maps and gradient bit for bit; the loss scalars and the weighted loss's S are
+ * sums over the forward kernel's units and differ in their last bits). */
 int32_t fgs_debug_set_option(int32_t key, int32_t value);
 
 #endif /* FGS_DEV_SWITCHES */
