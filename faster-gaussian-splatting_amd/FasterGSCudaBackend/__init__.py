@@ -18,8 +18,9 @@ from .fused import FusedRasterizerOptimizer  # noqa: E402
 from .aux_ops import add_noise, relocation_adjustment, update_3d_filter  # noqa: E402
 from .bilagrid import bilagrid_slice, bilagrid_tv_loss  # noqa: E402
 from .normals import gaussian_surface_features, normal_consistency  # noqa: E402
+from .tsdf import tsdf_extract_mesh, tsdf_integrate  # noqa: E402
 
 __all__ = ['diff_rasterize', 'diff_rasterize_aux', 'diff_rasterize_absgrad', 'diff_rasterize_pose', 'diff_rasterize_features', 'diff_rasterize_distortion', 'diff_rasterize_geometry', 'rasterize', 'rasterize_aux', 'update_pruning_scores', 'RasterizerSettings', 'FusedAdam', 'update_3d_filter',
            'relocation_adjustment', 'add_noise', 'FusedRasterizerOptimizer', 'ExtensionError', 'set_async_forward', 'async_forward_stats',
            'set_live_block_handover', 'live_block_stats', 'set_gradient_recycling', 'gradient_recycling_stats', 'take_async_overflow', 'async_forward_scope', 'bilagrid_slice', 'bilagrid_tv_loss',
-           'gaussian_surface_features', 'normal_consistency']
+           'gaussian_surface_features', 'normal_consistency', 'tsdf_integrate', 'tsdf_extract_mesh']

@@ -850,6 +850,68 @@ class Backend:
                                                              grad_map.data_ptr(), _stream_of(device)), 'fgs_normal_consistency_backward')
         return grad_map
 
+    # -- TSDF fusion and mesh extraction (include/fgs_hip.h, csrc/tsdf.hip) ------------------------------------------------------
+    @staticmethod
+    def _check_volume(tsdf_weight: torch.Tensor, color: Optional[torch.Tensor]) -> tuple:
+        """(device, (nx, ny, nz)) of a [nz,ny,nx,2] state tensor and, if given, its planar [3,nz,ny,nx] colour volume."""
+        if not isinstance(tsdf_weight, torch.Tensor) or tsdf_weight.dtype != torch.float32 or not tsdf_weight.is_contiguous() or tsdf_weight.dim() != 4 \
+                or tsdf_weight.shape[3] != 2:
+            raise RuntimeError('tsdf: tsdf_weight must be a contiguous float32 [nz, ny, nx, 2] tensor')
+        nz, ny, nx, _ = tsdf_weight.shape
+        if color is not None and (color.dtype != torch.float32 or not color.is_contiguous() or color.device != tsdf_weight.device
+                                  or tuple(color.shape) != (3, nz, ny, nx)):
+            raise RuntimeError(f'tsdf: color must be a contiguous float32 [3, {nz}, {ny}, {nx}] tensor on {tsdf_weight.device}')
+        return tsdf_weight.device, (int(nx), int(ny), int(nz))
+
+    def tsdf_integrate(self, tsdf_weight: torch.Tensor, color: Optional[torch.Tensor], origin: Sequence[float], voxel_size: float, trunc: float,
+                       settings_list: Sequence[RasterizerSettings], depths: Sequence[torch.Tensor], alphas: Optional[Sequence] = None,
+                       colors: Optional[Sequence] = None, near: Optional[float] = None, depth_max: float = math.inf, min_alpha: float = 0.5,
+                       max_weight: float = 65536.0) -> None:
+        """Folds 1..8 views of one size into the volume IN PLACE, one launch (fgs_tsdf_integrate). near: None = the first view's near plane."""
+        device, dims = self._check_volume(tsdf_weight, color)
+        k = len(settings_list)
+        if len(depths) != k or (alphas is not None and len(alphas) != k) or (colors is not None and len(colors) != k):
+            raise RuntimeError('tsdf_integrate: one depth (and opacity / colour) map per view')
+        if color is not None and colors is None:
+            raise RuntimeError('tsdf_integrate: the volume has colour, the views have no colour maps')
+        w, h = (int(settings_list[0].width), int(settings_list[0].height)) if k else (0, 0)
+        views, keep = (_lib.TsdfView * max(k, 1))(), []
+        for v, s in enumerate(settings_list):
+            if (int(s.width), int(s.height)) != (w, h):
+                raise RuntimeError('tsdf_integrate: the views of one call must have one image size')
+            maps = {'depth': (depths[v], (h, w)), 'alpha': (None if alphas is None else alphas[v], (h, w)), 'color': (None if colors is None else colors[v], (3, h, w))}
+            for name, (t, shape) in maps.items():
+                if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != device or tuple(t.shape) != shape):
+                    raise RuntimeError(f"tsdf_integrate: '{name}' of view {v} must be a contiguous float32 {shape} tensor on {device}")
+            w2c = s.w2c.to(device=device, dtype=torch.float32).contiguous()
+            if w2c.numel() < 12:
+                raise ValueError('w2c needs >= 3x4 entries')
+            keep.append(w2c)
+            views[v] = _lib.TsdfView(w2c.data_ptr(), float(s.focal_x), float(s.focal_y), float(s.center_x), float(s.center_y), depths[v].data_ptr(),
+                                     _ptr(maps['alpha'][0]), _ptr(maps['color'][0]))
+        near = float(settings_list[0].near_plane) if near is None and k else float(near or 0.0)
+        self._check(self.lib.fgs_tsdf_integrate(tsdf_weight.data_ptr(), _ptr(color), *dims, *[float(o) for o in origin], float(voxel_size), float(trunc),
+                                                views, k, w, h, near, float(depth_max), float(min_alpha), float(max_weight), _stream_of(device)),
+                    'fgs_tsdf_integrate')
+
+    def tsdf_extract_mesh(self, tsdf_weight: torch.Tensor, color: Optional[torch.Tensor], origin: Sequence[float], voxel_size: float, iso: float = 0.0,
+                          min_weight: float = 1.0) -> tuple:
+        """(vertices [Nv,3] float32, faces [Nf,3] int32, colors [Nv,3] float32 or None) of the level set: count (one host synchronisation), allocate, emit."""
+        device, dims = self._check_volume(tsdf_weight, color)
+        scratch = _empty_bytes(self.lib.fgs_tsdf_mesh_scratch_bytes(*dims), device)
+        counts = (C.c_int64 * 2)()
+        stream = _stream_of(device)
+        self._check(self.lib.fgs_tsdf_mesh_count(tsdf_weight.data_ptr(), *dims, float(iso), float(min_weight), scratch.data_ptr(), counts, stream),
+                    'fgs_tsdf_mesh_count')
+        nv, nf = int(counts[0]), int(counts[1])
+        vertices = torch.empty((nv, 3), dtype=torch.float32, device=device)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=device)
+        colors = torch.empty((nv, 3), dtype=torch.float32, device=device) if color is not None else None
+        self._check(self.lib.fgs_tsdf_mesh_emit(tsdf_weight.data_ptr(), _ptr(color), *dims, *[float(o) for o in origin], float(voxel_size), float(iso),
+                                                float(min_weight), scratch.data_ptr(), nv, nf, _ptr(vertices), _ptr(colors), _ptr(faces), stream),
+                    'fgs_tsdf_mesh_emit')
+        return vertices, faces, colors
+
     # -- Gaussian-sharded multi-GPU path (include/fgs_hip.h, "Gaussian-sharded multi-GPU path") --------------------------------
     def _settings_array(self, views: Sequence[RasterizerSettings], total_sh_rest: int, device: torch.device, keep: list):
         arr = (_lib.Settings * len(views))()

@@ -37,12 +37,18 @@ class StageTime(C.Structure):
     _fields_ = [('name', C.c_char_p), ('total_ms', C.c_double), ('calls', C.c_int64)]
 
 
+class TsdfView(C.Structure):          # fgs_tsdf_view
+    _fields_ = [('w2c', C.c_void_p), ('focal_x', C.c_float), ('focal_y', C.c_float), ('center_x', C.c_float), ('center_y', C.c_float),
+                ('depth', C.c_void_p), ('alpha', C.c_void_p), ('color', C.c_void_p)]
+
+
 class BlobEntry(C.Structure):
     _fields_ = [('name', C.c_char_p), ('offset', C.c_size_t), ('bytes', C.c_size_t)]
 
 
 SPLAT_RECORD_BYTES, ACC_RECORD_BYTES = 56, 36        # FGS_SPLAT_RECORD_BYTES / FGS_ACC_RECORD_BYTES
 DISTORTION_LINEAR, DISTORTION_NORMALIZED = 0, 1      # FGS_DISTORTION_*
+TSDF_MAX_VIEWS = 8                                   # FGS_TSDF_MAX_VIEWS
 
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
 
@@ -124,6 +130,10 @@ _SIGNATURES = {
     'fgs_surface_features_backward': (C.c_int32, [_P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     'fgs_normal_consistency': (C.c_int32, [_P, _I32, _I32] + [C.c_float] * 5 + [_P, _P, _P]),
     'fgs_normal_consistency_backward': (C.c_int32, [_P, _P, _I32, _I32] + [C.c_float] * 5 + [_P, _P]),
+    'fgs_tsdf_integrate': (C.c_int32, [_P, _P, _I32, _I32, _I32] + [C.c_float] * 5 + [C.POINTER(TsdfView), _I32, _I32, _I32] + [C.c_float] * 4 + [_P]),
+    'fgs_tsdf_mesh_scratch_bytes': (C.c_size_t, [_I32, _I32, _I32]),
+    'fgs_tsdf_mesh_count': (C.c_int32, [_P, _I32, _I32, _I32, C.c_float, C.c_float, _P, C.POINTER(_I64), _P]),
+    'fgs_tsdf_mesh_emit': (C.c_int32, [_P, _P, _I32, _I32, _I32] + [C.c_float] * 6 + [_P, _I64, _I64, _P, _P, _P, _P]),
     'fgs_profile_enable': (C.c_int32, [_I32]),
     'fgs_profile_read': (C.c_int32, [C.POINTER(StageTime), _I32]),
     'fgs_debug_wave_selftest': (C.c_int32, [_P, _P]),

@@ -1,4 +1,4 @@
-// What the host units of the C ABI share (api.hip, api_shard.hip, api_ops.hip, api_bilagrid.hip, api_normals.hip, api_debug.hip): the error channel, the stage timer, the blob
+// What the host units of the C ABI share (api.hip, api_shard.hip, api_ops.hip, api_bilagrid.hip, api_normals.hip, api_tsdf.hip, api_debug.hip): the error channel, the stage timer, the blob
 // carver with the five buffer layouts, and the argument builders. Internal: not installed, not seen by the kernel units.
 // The error text and the stage recorder are the library's only state; both live in api.hip, behind fail() and StageScope.
 #pragma once

@@ -355,6 +355,27 @@ hipError_t launch_surface_features_backward(const SurfaceFeatureArgs& a, hipStre
 hipError_t launch_normal_consistency(const NormalConsistencyArgs& a, hipStream_t s);
 hipError_t launch_normal_consistency_backward(const NormalConsistencyArgs& a, hipStream_t s);
 
+// tsdf.hip: fused TSDF integration of up to kTsdfMaxViews rendered views into a dense volume, and the marching-tetrahedra mesh of its level set
+constexpr int kTsdfMaxViews = 8;
+struct TsdfView { const float* w2c; float fx, fy, cx, cy; const float* depth; const float* alpha; const float* color; };   // w2c: device, rows 0..2; alpha / color may be nullptr
+struct TsdfIntegrateArgs {
+    float2* tsdf_weight; float* color;           // [nz,ny,nx] (tsdf, weight) pairs; planar [3,nz,ny,nx] or nullptr
+    int nx, ny, nz; float ox, oy, oz, voxel, trunc, inv_trunc;      // inv_trunc = 1 / trunc, rounded once on the host
+    int n_views, width, height;
+    float near_plane, depth_max, min_alpha, max_weight;
+    TsdfView view[kTsdfMaxViews];
+};
+hipError_t launch_tsdf_integrate(const TsdfIntegrateArgs& a, hipStream_t s);
+struct MeshArgs {
+    const float2* tsdf_weight; const float* color; int nx, ny, nz; float ox, oy, oz, voxel, iso, min_weight;
+    uint32_t* codes; uint2* block_sums; uint32_t* totals;       // scratch: a code word per lattice point, (vertices, triangles) per workgroup, the two totals
+    uint32_t n_vertices; uint64_t n_triangles;                  // emit: the sizes of the caller's buffers (nothing is written past them)
+    float* vertices; float* colors; int32_t* faces;             // emit: [Nv,3], [Nv,3] or nullptr, [Nf,3]
+};
+uint32_t mesh_blocks(uint32_t n_points);                        // workgroups (= block sums) of the two lattice passes
+hipError_t launch_tsdf_mesh_count(const MeshArgs& a, hipStream_t s);      // classify + scan: codes, block bases, totals
+hipError_t launch_tsdf_mesh_emit(const MeshArgs& a, hipStream_t s);       // from the scratch a count launch over the same volume left
+
 // shard_exchange.hip: record (un)packing either side of the two exchanges of the Gaussian-sharded multi-GPU path
 struct PackRecordsView { const PrimRec* rec; const uint32_t* n_touched; const uint32_t* depth_keys; const uint32_t* prim_idx;
                          const uint32_t* counters; uint32_t* slot; uint32_t* out; uint32_t* counts_out; };

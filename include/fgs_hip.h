@@ -627,6 +627,50 @@ int32_t fgs_normal_consistency(const float* surface_map, int32_t width, int32_t 
 int32_t fgs_normal_consistency_backward(const float* surface_map, const float* grad_consistency, int32_t width, int32_t height, float focal_x, float focal_y,
                                         float center_x, float center_y, float min_alpha, float* grad_map, void* stream);
 
+/* ---- TSDF fusion and mesh extraction (csrc/tsdf.hip; INTEGRATION.md "Surface extraction") ----
+ * Volume: a dense lattice of nx x ny x nz points, x fastest; point (i,j,k) lies at origin + voxel_size (i,j,k) in world space.
+ *   tsdf_weight  fp32 [nz,ny,nx,2]: tsdf in [-1,1] and the accumulated weight, 8-byte aligned;
+ *   color        fp32 PLANAR [3,nz,ny,nx] (a wave's 64 points are contiguous in every channel), or NULL.
+ * Zeroed buffers are an empty volume. Every call below refuses (FGS_ERR_INVALID_ARGUMENT, text in fgs_last_error, before anything touches the GPU)
+ * an extent < 2, nx ny nz > 2^28, voxel_size <= 0, a NULL required pointer and a misaligned tsdf_weight.
+ *
+ * fgs_tsdf_integrate folds n_views views (1..FGS_TSDF_MAX_VIEWS, all width x height) into the volume in ONE launch, in argument order. For a lattice
+ * point p and a view:  c = R p + t (w2c rows 0..2), z = c.z, skip if z <= near_plane;  u = focal_x c.x / z + center_x, v = focal_y c.y / z + center_y
+ * (the meaning of fgs_settings; pixel px covers [px, px + 1), the blend evaluates it at px + 0.5), px = floor(u), py = floor(v), skip outside the image;
+ * d = depth[py,px] (view-space z: fgs_inference_aux's median depth, or its expected depth divided by alpha), skip if d <= 0, d > depth_max, or
+ * alpha[py,px] < min_alpha where an opacity map is given;  sdf = d - z, skip if sdf < -trunc, f = min(1, sdf / trunc);  w' = w + 1,
+ * tsdf = (tsdf w + f) / w', colour likewise, w = min(w', max_weight). Nearest pixel, no interpolation. A point that no view of the call updates is
+ * not written. The kernel multiplies by fp32 reciprocals (1/z, 1/trunc, 1/w') where the formulas divide: a last-bit difference. One call with V views equals V single-view calls in the same order bit for bit. With a colour volume every view needs a colour map;
+ * without one the maps are ignored. Also refused: trunc <= 0, max_weight < 1, a non-positive image size, n_views outside 1..8, a view without w2c / depth. */
+#define FGS_TSDF_MAX_VIEWS 8
+typedef struct fgs_tsdf_view {
+    const float* w2c;                                /* DEVICE: row-major world-to-camera, rows 0..2 (12 floats) */
+    float focal_x, focal_y, center_x, center_y;
+    const float* depth;                              /* DEVICE [height, width] */
+    const float* alpha;                              /* DEVICE [height, width] or NULL */
+    const float* color;                              /* DEVICE [3, height, width] or NULL */
+} fgs_tsdf_view;
+int32_t fgs_tsdf_integrate(float* tsdf_weight, float* color, int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y, float origin_z,
+                           float voxel_size, float trunc, const fgs_tsdf_view* views, int32_t n_views, int32_t width, int32_t height, float near_plane,
+                           float depth_max, float min_alpha, float max_weight, void* stream);
+/* Mesh of the level set {tsdf = iso}: marching tetrahedra on the Kuhn split, no case table. A cube (i,j,k) is valid when its eight corners have
+ * weight >= min_weight; it is cut into six tetrahedra, one per permutation (p1,p2,p3) of the axes in lexicographic order: v0 = (0,0,0), v1 = v0 + e_p1,
+ * v2 = v1 + e_p2, v3 = (1,1,1). An edge runs from a lattice point a to b = a + d, d in {0,1}^3 \ {0} (type 1..7 = d.x + 2 d.y + 4 d.z) and is owned by
+ * a; it carries a vertex when both ends are valid and (f_a < iso) != (f_b < iso), at a + d voxel_size (iso - f_a) / (f_b - f_a), colour interpolated
+ * alike. Vertices are ordered by owner (linear lattice index), then type; triangles by cube, then tetrahedron (1 for a 1|3 split, 2 for 2|2); normals
+ * point from f < iso towards f >= iso. A corner with f == iso counts as outside, which yields zero-area triangles: they are KEPT, the index topology
+ * is closed because of them. Both orders are deterministic: two runs give the same bytes.
+ *   fgs_tsdf_mesh_count: classifies and scans into `scratch` (fgs_tsdf_mesh_scratch_bytes; 0 for a refused size; 8-byte aligned), then waits for
+ *     `stream` and returns the two sizes in HOST counts[2] = (n_vertices, n_triangles). (0, 0) is a normal result.
+ *   fgs_tsdf_mesh_emit: fills vertices [Nv,3], colors [Nv,3] (NULL = none; needs `color`) and faces [Nf,3] from the SAME volume, parameters and scratch
+ *     the count call saw; nothing is written past the given sizes. Sizes (0, 0) launch nothing; a NULL output with a non-zero size is refused. */
+size_t fgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t fgs_tsdf_mesh_count(const float* tsdf_weight, int32_t nx, int32_t ny, int32_t nz, float iso, float min_weight, void* scratch, int64_t* counts,
+                            void* stream);
+int32_t fgs_tsdf_mesh_emit(const float* tsdf_weight, const float* color, int32_t nx, int32_t ny, int32_t nz, float origin_x, float origin_y,
+                           float origin_z, float voxel_size, float iso, float min_weight, const void* scratch, int64_t n_vertices, int64_t n_triangles,
+                           float* vertices, float* colors, int32_t* faces, void* stream);
+
 /* Optional per-stage timing. While enabled (1), every pipeline stage is bracketed by hipEvents recorded on the caller's stream
  * (each event costs a few microseconds of GPU idle time: ~0.2 ms per training iteration with all stages on); enable = 2 + k brackets
  * only stage k (its index in the table fgs_profile_read returns), which leaves a timed loop practically undisturbed;
